@@ -8,7 +8,9 @@ per-GPU shard of BASELINE config C4 (12 500 problems x n=50 x m=2000, fp32; 8 ra
 100 000-problem C4) — weak scaling.  Problems shard across ranks with no data-path collective; one
 result gather (RCCL) runs after the timed region and is reported separately.
 
-Prints ONE JSON line on rank 0 (stdout); diagnostics go to stderr.
+Prints ONE JSON line on rank 0 (stdout); diagnostics go to stderr.  A plain run sets up, warms up, times --steps steps and
+prints the line; --full adds what takes work of its own outside the timed steps (the CPU baseline, the measured read ceilings of
+the roofline, large128's balanced batch).  --dump-outputs DIR writes the last timed step's results as .npy files.
 """
 from __future__ import annotations
 
@@ -57,6 +59,28 @@ MFMA_PEAK_TFLOPS = {"f32": 157.3, "f64": 78.6}
 
 def log(*a):
     print(*a, file=sys.stderr, flush=True)
+
+
+DUMP_BUDGET = 64 << 20
+
+
+def dump_outputs(out_dir, x, out):
+    """--dump-outputs: what the timed path handed its caller in its last step — the solution x and every Output tensor — as
+    out_dir/<name>.npy, fp32 results as float32 and everything else as float64 (integer fields convert exactly).  `counters`
+    is left out: it counts the library's work (passes, memo hits), not what it computed.  Past DUMP_BUDGET bytes in all, every
+    per-problem array keeps the same seeded sample of problems, so that two builds stay comparable row for row."""
+    arrays = {"x": x}
+    arrays.update({k: v for k, v in vars(out).items() if isinstance(v, torch.Tensor) and k != "counters"})
+    arrays = {k: v.detach().cpu().numpy() for k, v in arrays.items()}
+    arrays = {k: v if v.dtype == np.float32 else v.astype(np.float64) for k, v in arrays.items()}
+    P = x.shape[0]
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_BUDGET:
+        keep = np.sort(np.random.default_rng(0).choice(P, max(1, P * DUMP_BUDGET // total), replace=False))
+        arrays = {k: a[keep] if a.ndim and a.shape[0] == P else a for k, a in arrays.items()}
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{k}.npy"), np.ascontiguousarray(a))
 
 
 def eigen_probe():
@@ -213,6 +237,8 @@ def run_single(args, ta, rank, world, local_rank):
         dist.barrier(device_ids=[local_rank])
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, xs[-1], outs[-1])
     timed = outs[nwarm:]
     iters_total = int(sum(int(o.num_iters.sum().item()) for o in timed))
     passes_total = int(sum(int((o.counters[0] + o.counters[1]).item()) for o in timed))
@@ -260,7 +286,7 @@ def run_single(args, ta, rank, world, local_rank):
                              "hand-overs; the figure of merit is us per LM iteration, GB/s is reported for scale only",
                      "algorithmic_bytes_per_pass": bytes_per_pass, "kernel_us_all": kern_us},
     }
-    if not args.no_cpu and world == 1:
+    if args.full and not args.no_cpu and world == 1:
         from oracle import pyoracle   # the checker / CPU baseline only: the inputs above came from the package's own generators
         lib = pyoracle.load(pyoracle.build(march="native", out_dir=tempfile.mkdtemp(prefix="toa_oracle_")))
         x0h = x0.cpu().numpy()
@@ -336,6 +362,8 @@ def run_ba(args, ta, rank, world, local_rank):
         dist.barrier(device_ids=[local_rank])
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, x, out)
     iters_total = int(sum(int(r[2].item()) for r in recs))
     passes_total = int(sum(int(r[3].item()) for r in recs))
     kern_ms = [r[0].elapsed_time(r[1]) for r in recs]
@@ -388,7 +416,7 @@ def run_ba(args, ta, rank, world, local_rank):
                              "(profiles/r02_pmc_ba_before.json); the kernel is latency / issue-bound now, DESIGN.md 4c",
                      "kernel_ms_avg": kern_s * 1e3, "kernel_ms_all": kern_ms},
     }
-    if not args.no_cpu and world == 1:
+    if args.full and not args.no_cpu and world == 1:
         from oracle import pyoracle
         lib = pyoracle.load(pyoracle.build(march="native", out_dir=tempfile.mkdtemp(prefix="toa_oracle_")))
         S = args.cpu_problems or 6
@@ -449,6 +477,8 @@ def run_balists(args, ta, rank, world, local_rank):
         dist.barrier(device_ids=[local_rank])
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, x, out)
     iters_total = int(sum(int(r[2].item()) for r in recs))
     passes_total = int(sum(int(r[3].item()) for r in recs))
     kern_ms = [r[0].elapsed_time(r[1]) for r in recs]
@@ -499,7 +529,7 @@ def run_balists(args, ta, rank, world, local_rank):
                              "iteration; GB/s is reported for scale only",
                      "kernel_ms_avg": kern_s * 1e3, "kernel_ms_all": kern_ms},
     }
-    if not args.no_cpu and world == 1:
+    if args.full and not args.no_cpu and world == 1:
         from oracle import pyoracle
         lib = pyoracle.load(pyoracle.build(march="native", out_dir=tempfile.mkdtemp(prefix="toa_oracle_")))
         Cs, Ns = 16, 300
@@ -526,7 +556,12 @@ def main():
     ap.add_argument("--workload", default="c4", choices=sorted(WORKLOADS) + sorted(SINGLE) + ["ba", "balists"])
     ap.add_argument("--problems", type=int, default=0, help="override problems per GPU (debug; invalidates the metric)")
     ap.add_argument("--cpu-problems", type=int, default=0, help="CPU baseline sample size (0 = auto)")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline leg (profiling runs)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: the cpu_baseline leg, the HBM / on-die read ceilings of "
+                         "the roofline, the balanced batch of large128 (all of them outside the timed steps)")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the cpu_baseline leg")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last step computed (x and the Output tensors) as DIR/<name>.npy")
     ap.add_argument("--loss", default="", help="an M-estimator on every residual of a packed DenseRow workload (c4, c3), e.g. huber:0.5 — "
                                                "losses::Huber(n2, th2, true) inside the cost functor (robust_norms.h:20-26); recorded in the line")
     ap.add_argument("--dry-run", action="store_true",
@@ -536,6 +571,8 @@ def main():
     ap.add_argument("--tuning", default="", help="A/B arms of the library as toa_tuning fields, e.g. coop_off=1,memo_off=1 (recorded in the line; "
                                                  "the default line is measured with none)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -663,6 +700,8 @@ def main():
     sync()
     elapsed = time.perf_counter() - t0
     elapsed_local = elapsed
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, x, out)
     iters_total = int(acc[0].item())
     passes_total = int(acc[1].item())
     acc_passes_total = int(acc[3].item())
@@ -776,29 +815,26 @@ def main():
             dist.destroy_process_group()
         return
 
-    # measured STREAM-like read ceiling over the same packed buffer, next to the nominal peak
-    try:
-        if not gpu:
-            raise RuntimeError("dry run")
-        probe_src = model.packed
-        if large:   # (a slice of whole problems, at most ~1 GiB; the natural layout's rows are 4 (n + 1)-byte records: cut on a 16-byte boundary)
-            rows = max(1, min(probe_src.shape[0], (1 << 30) // max(1, probe_src.shape[1] * probe_src.element_size())))
-            probe_src = probe_src[:rows]
-        nb = probe_src.numel() * probe_src.element_size() // 16 * 16
-        out_gbs = ctypes.c_double()
-        ta.api.check(ctx.lib.toa_hbm_read_probe(ctx.h, ctypes.c_void_p(probe_src.data_ptr()), nb, 5, ctypes.byref(out_gbs)))
-        stream_read = out_gbs.value
-    except Exception as e:  # noqa: BLE001
-        log(f"[bench] hbm read probe failed: {e}")
-        stream_read = None
-    # the same for a working set that stays on-die (the 256 MiB Infinity Cache): the ceiling of re-reads, next to HBM's
-    try:
-        if not gpu:
-            raise RuntimeError("dry run")
-        llc_read = ctx.llc_read_GBps(model.packed)
-    except Exception as e:  # noqa: BLE001
-        log(f"[bench] llc read probe failed: {e}")
-        llc_read = None
+    # the read ceilings are runs of their own on the device (--full only; null in a plain line)
+    stream_read = llc_read = None
+    if args.full and gpu:
+        # measured STREAM-like read ceiling over the same packed buffer, next to the nominal peak
+        try:
+            probe_src = model.packed
+            if large:   # (a slice of whole problems, at most ~1 GiB; the natural layout's rows are 4 (n + 1)-byte records: cut on a 16-byte boundary)
+                rows = max(1, min(probe_src.shape[0], (1 << 30) // max(1, probe_src.shape[1] * probe_src.element_size())))
+                probe_src = probe_src[:rows]
+            nb = probe_src.numel() * probe_src.element_size() // 16 * 16
+            out_gbs = ctypes.c_double()
+            ta.api.check(ctx.lib.toa_hbm_read_probe(ctx.h, ctypes.c_void_p(probe_src.data_ptr()), nb, 5, ctypes.byref(out_gbs)))
+            stream_read = out_gbs.value
+        except Exception as e:  # noqa: BLE001
+            log(f"[bench] hbm read probe failed: {e}")
+        # the same for a working set that stays on-die (the 256 MiB Infinity Cache): the ceiling of re-reads, next to HBM's
+        try:
+            llc_read = ctx.llc_read_GBps(model.packed)
+        except Exception as e:  # noqa: BLE001
+            log(f"[bench] llc read probe failed: {e}")
     # secondary ceiling ("MFMA ceiling reported additionally"): matrix-core flops ISSUED by the accumulate
     # passes (NBM(NBM+1)/2 tiles of v_mfma_*_16x16x4 = 2048 flop per 4 rows) against the dense fp32 / fp64 MFMA peak
     if large:
@@ -901,7 +937,7 @@ def main():
                                                 "passes_per_launch": r["passes_per_launch"],
                                                 "measured_read_ceiling_GBps": r["measured_read_ceiling_GBps"],
                                                 "llc_read_ceiling_GBps": r["llc_read_ceiling_GBps"]}}
-    if args.workload == "large128" and gpu and world == 1 and not args.no_cpu:   # (--no-cpu = a profiling run: only the launches of the timed workload)
+    if args.workload == "large128" and gpu and world == 1 and args.full and not args.no_cpu:   # (--no-cpu = a profiling run: only the launches of the timed workload)
         # 512 problems = 256 CUs x 2 resident workgroups: every slot holds exactly ONE problem, so the launch lasts as long as the CU
         # with the two longest ones (iterations per problem: mean 7.3, max 10-11).  The kernel's own rate shows on a batch that keeps
         # the slots refilled — the same generator at four times the problems, after the timed region (profiles/r06_ab_log.md §4):
@@ -933,7 +969,7 @@ def main():
                                                 "lm_iterations_per_s": float(ob.num_iters.sum()) / tb_s,
                                                 "frac": accp * result["roofline"]["flop_per_accumulate_pass"] / tb_s / 1e12 / result["roofline"]["peak"]}
         del mb, xb, x0b, ob
-    if not args.no_cpu and world == 1:  # the CPU baseline leg runs on rank 0 at N = 1 only
+    if args.full and not args.no_cpu and world == 1:  # the CPU baseline leg runs on rank 0 at N = 1 only
         np_dtype = np.float32 if tdt == torch.float32 else np.float64
         est = 4e-4 * (n * n * m) / (50 * 50 * 2000) * 8  # rough seconds per problem (8 iterations)
         sample = args.cpu_problems or int(max(16, min(P, 15.0 / max(est, 1e-6))))

@@ -153,3 +153,23 @@ def test_bench_dry_run_two_ranks():
 
 def test_bench_dry_run_eight_ranks():
     _dry_run(8)
+
+
+def test_bench_dump_outputs(built, tmp_path):
+    """`bench.py --dump-outputs DIR` (through --dry-run's stand-in solve): --steps timed steps in the line, and the last step's x and
+    Output tensors in DIR as .npy — fp32 results as float32, the rest as float64, `counters` (work done, not results) left out."""
+    import json
+    import subprocess
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--dry-run", "--dump-outputs", str(tmp_path)]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-3000:]
+    d = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+    assert d["steps"] == 2 and d["ms_per_step"] > 0
+    assert sorted(os.listdir(tmp_path)) == ["final_cost.npy", "num_iters.npy", "stop_reason.npy", "x.npy"]
+    P = d["config"]["problems_per_gpu"]
+    x = np.load(tmp_path / "x.npy")
+    assert x.dtype == np.float32 and x.shape == (P, d["config"]["n"])
+    assert np.allclose(x, np.arange(P)[:, None] * 0.001 + np.arange(x.shape[1])[None, :], rtol=0, atol=1e-5)   # the planted x*
+    for name, want in (("stop_reason", 3.0), ("num_iters", 7.0)):
+        a = np.load(tmp_path / f"{name}.npy")
+        assert a.dtype == np.float64 and a.shape == (P,) and (a == want).all()

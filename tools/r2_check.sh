@@ -6,7 +6,7 @@ mkdir -p $O
 cd $R
 python -m pytest tests -m gpu -x -q -s 2>&1 | tail -40 > $O/pytest_gpu.txt
 for wl in c4 c3 c2 c5 c1; do
-  python bench.py --workload $wl > $O/bench_$wl.json 2> $O/bench_$wl.err
+  python bench.py --workload $wl --full > $O/bench_$wl.json 2> $O/bench_$wl.err
 done
 tail -5 $O/pytest_gpu.txt
 for wl in c4 c3 c2 c5 c1; do python - <<PY

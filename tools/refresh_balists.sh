@@ -6,7 +6,7 @@ R=${GRAFT_REPO_ROOT:-$PWD}
 O=$R/gpurun_out/refresh
 mkdir -p $O
 cd $R
-python bench.py --workload balists > $O/bench_balists.json 2> $O/bench_balists.err
+python bench.py --workload balists --full > $O/bench_balists.json 2> $O/bench_balists.err
 python bench.py --workload balists --no-cpu --tuning large_library_solver=1 > $O/bench_balists_rocsolver.json 2>/dev/null
 cd /tmp && export TMPDIR=/tmp
 rm -rf $O/stats_balists

@@ -2,7 +2,7 @@
 # targeted refresh of the evidence the n > 128 / BA-lists solver touches (run through gpurun): same outputs, same names as
 # tools/refresh_profiles.sh leaves under gpurun_out/refresh, so that tools/digest_profiles.py picks them up
 R=${GRAFT_REPO_ROOT:-$PWD}; O=$R/gpurun_out/refresh; mkdir -p $O; cd $R
-for wl in large256 balists; do python bench.py --workload $wl $( [ $wl = large256 ] && echo "--steps 5 --warmup 2" ) > $O/bench_$wl.json 2> $O/bench_$wl.err; done
+for wl in large256 balists; do python bench.py --workload $wl --full $( [ $wl = large256 ] && echo "--steps 5 --warmup 2" ) > $O/bench_$wl.json 2> $O/bench_$wl.err; done
 python bench.py --workload large256 --steps 5 --warmup 2 --no-cpu --tuning large_library_solver=1 > $O/bench_large256_rocsolver.json 2>/dev/null
 python bench.py --workload balists --no-cpu --tuning large_library_solver=1 > $O/bench_balists_rocsolver.json 2>/dev/null
 python bench.py --workload large256 --steps 5 --warmup 2 --no-cpu --tuning large_one_lane=1 > $O/bench_large256_one_lane.json 2>/dev/null

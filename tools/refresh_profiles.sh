@@ -7,14 +7,14 @@ O=$R/gpurun_out/refresh
 rm -rf $O; mkdir -p $O   # NOTE: also delete the LOCAL gpurun_out/refresh before calling gpurun (results are merged, not mirrored)
 cd $R
 python -m pytest tests -m gpu -q 2>&1 | grep -E "passed|failed|error" | tail -3 > $O/pytest_gpu.txt
-for wl in c4 c3 c2 c5 c1 ba balists c4_text c4_ad c2_batch_f32 c2_batch; do python bench.py --workload $wl > $O/bench_$wl.json 2> $O/bench_$wl.err; done
+for wl in c4 c3 c2 c5 c1 ba balists c4_text c4_ad c2_batch_f32 c2_batch; do python bench.py --workload $wl --full > $O/bench_$wl.json 2> $O/bench_$wl.err; done
 python tools/row_model_bench.py 12500 > $O/row_model_bench.txt 2>&1
-python bench.py --workload c4 --loss huber:0.5 > $O/bench_c4_huber.json 2> $O/bench_c4_huber.err
+python bench.py --workload c4 --loss huber:0.5 --full > $O/bench_c4_huber.json 2> $O/bench_c4_huber.err
 python bench.py --workload c4 --loss huber:0.5 --no-cpu --tuning narrow_mfma_pass=1 > $O/bench_c4_huber_old_route.json 2>/dev/null
 python bench.py --workload c3 --loss huber:0.5 --no-cpu > $O/bench_c3_huber.json 2>/dev/null
 python bench.py --workload c3 --loss huber:0.5 --no-cpu --tuning narrow_mfma_pass=1 > $O/bench_c3_huber_old_route.json 2>/dev/null
-python bench.py --workload large128 --steps 5 --warmup 2 > $O/bench_large128.json 2> $O/bench_large128.err
-python bench.py --workload large256 --steps 5 --warmup 2 > $O/bench_large256.json 2> $O/bench_large256.err
+python bench.py --workload large128 --steps 5 --warmup 2 --full > $O/bench_large128.json 2> $O/bench_large128.err
+python bench.py --workload large256 --steps 5 --warmup 2 --full > $O/bench_large256.json 2> $O/bench_large256.err
 python bench.py --workload large256 --steps 5 --warmup 2 --no-cpu --tuning large_library_solver=1 > $O/bench_large256_rocsolver.json 2>/dev/null
 python bench.py --workload balists --no-cpu --tuning large_library_solver=1 > $O/bench_balists_rocsolver.json 2>/dev/null
 python bench.py --workload large128 --steps 5 --warmup 2 --no-cpu --tuning large_row_split=1 > $O/bench_large128_rowsplit.json 2>/dev/null

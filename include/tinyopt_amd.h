@@ -108,7 +108,7 @@ extern "C" {
  * Not mirrored (host-side concerns, evaluated by the header adaptor between launches or unsupported
  * on the device path): log.*, stop_callback, stop_callback2, max_duration_ms. */
 typedef struct toa_options {
-  int32_t solver_type;          /* 0 LevenbergMarquardt, 1 GaussNewton            options.h:24-30 */
+  int32_t solver_type;          /* 0 LevenbergMarquardt, 1 GaussNewton, 2 GradientDescent (toa_jit_gd_run) options.h:24-30 */
   int32_t max_iters;            /* uint16 in the reference, default 50           options.h:89   */
   float min_error;              /* 1e-12f                                        options.h:90   */
   float min_rerr_dec;           /* 1e-10f                                        options.h:91   */
@@ -166,7 +166,7 @@ int toa_create(toa_handle* out, int device, void* stream);
 /* ---- ABI version.  4 (round 4): counters_dev arrays are [TOA_NUM_COUNTERS = 8] uint64 (they were [4] up to version 2 — a caller
  *      that still allocates 4 entries would be written out of bounds by the memo counter), toa_tuning / toa_jit_spec exist.
  *      The host mirrors (include/tinyopt_amd/tinyopt.hpp, tinyopt_amd/_capi.py) refuse a library whose version differs. */
-#define TOA_ABI_VERSION 6
+#define TOA_ABI_VERSION 7   /* 7: toa_gd_options, toa_jit_gd_run, TOA_JIT_COST / TOA_JIT_COST_GRAD */
 int toa_abi_version(void);
 
 /* ---- tuning (per handle).  The arms of the A/B logs (profiles/r0N_ab_log.md) and of the bit-identity tests, as typed state
@@ -509,6 +509,18 @@ int toa_model_compile(toa_handle h, int dtype, int num_params, int residuals_per
 #define TOA_MANIFOLD_USER 2   /* spec.plus_body + spec.x_scalars: a user parameter container (traits::params_trait<T>, traits.h:103-359) */
 #define TOA_JIT_RESIDUAL 0
 #define TOA_JIT_ACCUMULATE 1
+/* Scalar cost kinds (ABI 7) — the first-order half of the reference's Optimize (optimize.h:59-72, solvers/gd.h): the body assigns
+ * `c`, the item's cost term; the problem's cost is sum_i c_i (ONE residual: Cost(Scalar), cost.h:22).  Euclidean parameters and
+ * residuals_per_item = 1 only (anything else is refused with TOA_E_ARG); any 1 <= num_params <= 63.
+ *   TOA_JIT_COST       `f(x) -> scalar`: c written over the scalar type S (Jets for the gradient — beyond 12 parameters one
+ *                      evaluation per chunk of <= 12 seeded columns —, plain T cost-only); x[j], p[k], h[k] as for residual bodies.
+ *   TOA_JIT_COST_GRAD  `f(x, grad) -> scalar` (tests/unconstrained.cpp:19-42): c on plain T and, inside `if (want_grad) { ... }`,
+ *                      the item's own gradient ADDED to G[a].
+ * Such a model runs under solver_type = 2 through toa_jit_gd_run only (LM / GN entry points refuse it, as optimize.h:41-56 does),
+ * on a handle without a loss (toa_set_loss: a scalar cost has no residuals to robustify).  toa_jit_accumulate on it is
+ * SolverGD::Build's accumulation: g = sum_i grad c_i, cost = sum_i c_i, nres = 1; H_dev must be NULL. */
+#define TOA_JIT_COST 2
+#define TOA_JIT_COST_GRAD 3
 typedef struct toa_jit_spec {
   int32_t dtype, num_params, residuals_per_item, scalars_per_item, header_scalars;
   int32_t manifold;   /* TOA_MANIFOLD_* */
@@ -532,6 +544,18 @@ int toa_jit_lm_run(toa_handle h, toa_jit_model model, int num_items, int64_t P, 
                    const toa_options* options, const toa_results* results, uint64_t* counters_dev);
 int toa_jit_accumulate(toa_handle h, toa_jit_model model, int num_items, int64_t P, const void* data_dev, const void* x_dev,
                        int want_grad, void* g_dev, void* H_dev, double* cost_dev, int32_t* nres_dev);
+/*      Gradient descent (ABI 7): Optimize(x, cost, options) with options.solver_type = GradientDescent on a scalar cost model —
+ *      gd::Optimizer = Optimizer_<SolverGD> (optimizers/gd.h; optimizer.h:242-539): every Step builds g = sum_i grad c_i (clamped by
+ *      grad_clipping), dx = -lr * g, and judges, rolls back and stops exactly as the LM path does; no final Hessian is written
+ *      (results->final_hessian is left untouched, optimizer.h:313), the inlier ratio is 1.  One wavefront per problem, one launch.
+ *      toa_gd_options mirrors Options::GD (options.h:147-154); toa_options stays as it is.  options->solver_type must be 2. */
+typedef struct toa_gd_options {
+  float lr;              /* learning rate, 1e-3f (a float, promoted to the scalar type: options.h:148) */
+  int32_t reserved[7];
+} toa_gd_options;
+void toa_gd_options_default(toa_gd_options* o);
+int toa_jit_gd_run(toa_handle h, toa_jit_model model, int num_items, int64_t P, const void* data_dev, void* x_dev,
+                   const toa_options* options, const toa_gd_options* gd, const toa_results* results, uint64_t* counters_dev);
 /*      Row-split execution of a run-time model (any num_params; beyond 15 always the launch-per-iteration form) for FEW, HUGE problems — the reference's one `Optimize(x, cost)`
  *      over tens of thousands of residuals (BASELINE C2 / C5 shapes) with the residual supplied as text: the contract of
  *      toa_lm_run_split.  The items of each problem are cut into `splits` chunks (0 = chosen automatically), a wavefront per

@@ -40,7 +40,7 @@ enum StopReason : int {  // include/tinyopt/stop_reasons.h:14-43
 };
 
 struct Options {  // include/tinyopt/optimizers/options.h:18-156 (numeric knobs)
-  enum Solver { LevenbergMarquardt = 0, GaussNewton = 1 };
+  enum Solver { LevenbergMarquardt = 0, GaussNewton = 1, GradientDescent = 2 };   // GradientDescent: scalar cost models (TOA_JIT_COST*)
   Solver solver_type = LevenbergMarquardt;
   bool check_final_cost = false;
   bool use_step_quality_approx = false;
@@ -90,6 +90,15 @@ struct Options {  // include/tinyopt/optimizers/options.h:18-156 (numeric knobs)
     float good_factor = 1.0f / 3.0f;
     float bad_factor = 2.0f;
   } lm;
+  struct GD {   // options.h:147-154
+    float lr = 1e-3f;
+  } gd;
+  toa_gd_options gd_pod() const {
+    toa_gd_options g;
+    toa_gd_options_default(&g);
+    g.lr = gd.lr;
+    return g;
+  }
 
   toa_options to_pod() const {
     toa_options p;
@@ -449,6 +458,10 @@ BatchOutput Optimize(std::vector<Scalar>& x, const Cost& cost, const Options& op
   const int n = cost.n();
   if (int64_t(x.size()) != P * cost.xdim())
     throw std::invalid_argument("tinyopt_amd::Optimize: x must hold P * (parameters per problem) scalars");
+  const bool gd = options.solver_type == Options::GradientDescent;
+  if (gd && options.has_host_controls())
+    throw std::invalid_argument("tinyopt_amd::Optimize: GradientDescent runs as one launch per solve: stop callbacks, max_duration_ms "
+                                "and the log line are not supported on this path");
   if (options.has_host_controls()) {
     return OptimizeWithHostControls(x, cost, options, history);   // (run-time models too: toa_jit_lm_begin / step / stop)
   }
@@ -466,7 +479,8 @@ BatchOutput Optimize(std::vector<Scalar>& x, const Cost& cost, const Options& op
   r.final_rerr_dec = fr.data();
   r.final_inlier_ratio = inl.data();
   BatchOutput out;
-  if (options.hessian.save_last) { fH = DeviceBuffer<double>(ctx, size_t(P) * n * n); fH.zero(); r.final_hessian = fH.data(); }
+  const bool save_H = options.hessian.save_last && !gd;   // (no final Hessian on the first-order path: optimizer.h:313)
+  if (save_H) { fH = DeviceBuffer<double>(ctx, size_t(P) * n * n); fH.zero(); r.final_hessian = fH.data(); }
   if (history) {
     out.hist_stride = options.max_iters + 2;
     errs = DeviceBuffer<double>(ctx, size_t(P) * out.hist_stride); errs.zero();
@@ -476,9 +490,14 @@ BatchOutput Optimize(std::vector<Scalar>& x, const Cost& cost, const Options& op
   }
   const toa_options pod = options.to_pod();
   apply_loss(cost);
-  if constexpr (detail::is_jit<Cost>::value)
-    check(toa_jit_lm_run(ctx.get(), cost.jit_handle(), cost.items(), P, cost.data(), dx.data(), &pod, &r, nullptr));
-  else
+  if constexpr (detail::is_jit<Cost>::value) {
+    if (gd) {   // gd::Optimizer on a scalar cost model (the library refuses any other model: optimize.h:59-75)
+      const toa_gd_options gpod = options.gd_pod();
+      check(toa_jit_gd_run(ctx.get(), cost.jit_handle(), cost.items(), P, cost.data(), dx.data(), &pod, &gpod, &r, nullptr));
+    } else {
+      check(toa_jit_lm_run(ctx.get(), cost.jit_handle(), cost.items(), P, cost.data(), dx.data(), &pod, &r, nullptr));
+    }
+  } else
     check(toa_lm_run(ctx.get(), Cost::model_id, dtype_of<Scalar>(), n, cost.m(), P, cost.data(), dx.data(), &pod, &r, nullptr));
   check(toa_synchronize(ctx.get()));
   dx.download(x.data());
@@ -486,7 +505,7 @@ BatchOutput Optimize(std::vector<Scalar>& x, const Cost& cost, const Options& op
   get(out.stop_reason, stop); get(out.num_iters, iters); get(out.num_failures, fails);
   get(out.num_consec_failures, cfails); get(out.final_num_residuals, nres); get(out.final_cost, fc);
   get(out.final_rerr_dec, fr); get(out.final_inlier_ratio, inl);
-  if (options.hessian.save_last) get(out.final_hessian, fH);
+  if (save_H) get(out.final_hessian, fH);
   if (history) { get(out.errs, errs); get(out.deltas2, d2); get(out.successes, succ); }
   return out;
 }

@@ -58,7 +58,7 @@ class ToaResults(C.Structure):
 
 
 # every symbol include/tinyopt_amd.h declares: name -> (restype, argtypes)
-ABI_VERSION = 6   # include/tinyopt_amd.h TOA_ABI_VERSION
+ABI_VERSION = 7   # include/tinyopt_amd.h TOA_ABI_VERSION
 
 
 class ToaTuning(C.Structure):   # include/tinyopt_amd.h toa_tuning
@@ -71,6 +71,10 @@ class ToaJitSpec(C.Structure):   # include/tinyopt_amd.h toa_jit_spec
     _fields_ = [("dtype", C.c_int32), ("num_params", C.c_int32), ("residuals_per_item", C.c_int32), ("scalars_per_item", C.c_int32),
                 ("header_scalars", C.c_int32), ("manifold", C.c_int32), ("kind", C.c_int32), ("x_scalars", C.c_int32),
                 ("plus_body", C.c_char_p), ("reserved", C.c_int32 * 6)]
+
+
+class ToaGdOptions(C.Structure):   # include/tinyopt_amd.h toa_gd_options (Options::GD, options.h:147-154)
+    _fields_ = [("lr", C.c_float), ("reserved", C.c_int32 * 7)]
 
 
 _P = C.c_void_p
@@ -128,6 +132,8 @@ PROTOTYPES = {
     "toa_model_destroy": (C.c_int, [_P]),
     "toa_jit_lm_run": (C.c_int, [_P, _P, C.c_int, C.c_int64, _P, _P, C.POINTER(ToaOptions), C.POINTER(ToaResults), _P]),
     "toa_jit_accumulate": (C.c_int, [_P, _P, C.c_int, C.c_int64, _P, _P, C.c_int, _P, _P, _P, _P]),
+    "toa_gd_options_default": (None, [C.POINTER(ToaGdOptions)]),
+    "toa_jit_gd_run": (C.c_int, [_P, _P, C.c_int, C.c_int64, _P, _P, C.POINTER(ToaOptions), C.POINTER(ToaGdOptions), C.POINTER(ToaResults), _P]),
     "toa_jit_lm_run_split": (C.c_int, [_P, _P, C.c_int, C.c_int64, _P, _P, C.POINTER(ToaOptions), C.POINTER(ToaResults), _P, C.c_int]),
     "toa_jit_lm_begin": (C.c_int, [_P, _P, C.c_int, C.c_int64, _P, _P, C.POINTER(ToaOptions), C.POINTER(ToaResults), _P]),
     "toa_jit_lm_step": (C.c_int, [_P, _P, C.c_int, C.c_int64, _P, _P, C.POINTER(ToaOptions), C.POINTER(ToaResults), _P, _P, _P]),

@@ -62,6 +62,11 @@ class _LM:  # options.h:127-141
 
 
 @dataclass
+class _GD:  # options.h:147-154 — Options::GD
+    lr: float = 1e-3   # learning rate (a float in the reference: promoted to the scalar type of x)
+
+
+@dataclass
 class _Log:  # options.h:113-125 — the per-iteration log line of Optimizer_::Step (optimizer.h:463-516)
     enable: bool = False           # (the reference logs by default; a batched solve does not: one line per problem and iteration)
     e: str = "\u03b5\u00b2"          # symbol of the error in the line
@@ -84,6 +89,7 @@ class Options:
     ``print_failure`` are not mirrored)."""
     LevenbergMarquardt = 0
     GaussNewton = 1
+    GradientDescent = 2   # scalar cost models only (JitResidual kind="cost" / "cost_grad"): optimize.h:59-72
     solver_type: int = 0
     check_final_cost: bool = False
     use_step_quality_approx: bool = False
@@ -101,6 +107,7 @@ class Options:
     stop_callback: Optional[object] = None     # options.h:97-101  bool(err, |dx|^2, |g|^2)
     stop_callback2: Optional[object] = None    # options.h:102-106 bool(err, dx, g)
     lm: _LM = field(default_factory=_LM)
+    gd: _GD = field(default_factory=_GD)
     log: _Log = field(default_factory=_Log)
 
     def has_host_controls(self) -> bool:
@@ -479,10 +486,22 @@ class JitResidual:
             prior = ta.JitResidual(SE3_PRIOR_BODY, n=6, item_scalars=0, residuals_per_item=6, header_scalars=12, manifold="se3")
 
       * ``kind="accumulate"`` — a manual Accumulate callback (docs/API.md:37-57): the body fills ``r[q]`` and, inside
-        ``if (want_grad) { ... }``, its own Jacobian rows ``J[q][a]`` (plain T, no AD)."""
+        ``if (want_grad) { ... }``, its own Jacobian rows ``J[q][a]`` (plain T, no AD).
+
+    Scalar costs (the first-order half of the reference's ``Optimize``, optimize.h:59-72, solvers/gd.h) — run with
+    ``options.solver_type = Options.GradientDescent`` (``options.gd.lr``); Euclidean parameters, one "residual" per item:
+      * ``kind="cost"`` — ``f(x) -> scalar``: the body assigns ``c``, the item's cost term, over the scalar type ``S``
+        (differentiated on Jets); the problem's cost is the sum over its items.  Logistic regression::
+
+            logit = ta.JitResidual("S z = S(0); for (int j = 0; j < 12; ++j) z += p[j] * x[j]; "
+                                   "c = log(S(1) + exp(-p[12] * z));", n=12, item_scalars=13, kind="cost", dtype=torch.float32)
+
+      * ``kind="cost_grad"`` — ``f(x, grad) -> scalar`` (tests/unconstrained.cpp:19-42): ``c`` on plain T and, inside
+        ``if (want_grad) { ... }``, the item's own gradient added to ``G[a]``."""
 
     MANIFOLDS = {"euclid": 0, "se3": 1, "user": 2}
-    KINDS = {"residual": 0, "accumulate": 1}
+    KINDS = {"residual": 0, "accumulate": 1, "cost": 2, "cost_grad": 3}
+    COST_KINDS = ("cost", "cost_grad")
 
     def __init__(self, body: str, n: int, item_scalars: int, residuals_per_item: int = 1, header_scalars: int = 0,
                  dtype: torch.dtype = torch.float64, ctx: Optional["Context"] = None, manifold: str = "euclid", kind: str = "residual",
@@ -496,6 +515,8 @@ class JitResidual:
         self.ctx = ctx or default_context()
         self.n, self.kR, self.kD, self.kH, self.dtype = int(n), int(residuals_per_item), int(item_scalars), int(header_scalars), dtype
         self.manifold, self.kind = manifold, kind
+        if kind not in self.KINDS:
+            raise ValueError(f"unknown kind {kind!r}; one of {sorted(self.KINDS)}")
         self.xdim = 12 if manifold == "se3" else (int(x_scalars) if manifold == "user" else self.n)
         self._h = C.c_void_p()
         log = C.create_string_buffer(1 << 16)
@@ -843,6 +864,8 @@ def Optimize(x: torch.Tensor, cost, options: Optional[Options] = None, *, histor
                                        cost.obs_cam.data_ptr(), cost.obs_pt.data_ptr(), cost.obs_uv.data_ptr(), x.data_ptr(),
                                        C.byref(pod), C.byref(res), out.counters.data_ptr(), float(options.max_duration_ms or 0.0)))
         return out
+    if isinstance(cost, JitModel) and cost.res.kind in JitResidual.COST_KINDS and options.solver_type == Options.GradientDescent:
+        return _optimize_gd(x, cost, options, history, ctx, out, splits, zero_counters)
     if isinstance(cost, JitModel):
         if options.has_host_controls():   # the stepping form of the run-time model (toa_jit_lm_begin / step / stop)
             if splits is not None or out is not None:
@@ -879,6 +902,35 @@ def Optimize(x: torch.Tensor, cost, options: Optional[Options] = None, *, histor
     else:                # explicit row-split execution with `splits` chunks per problem (0 = automatic count)
         check(ctx.lib.toa_lm_run_split(ctx.h, cost.model_id, _dtype_code(x.dtype), n, cost.m, P, cost.packed.data_ptr(),
                                        x.data_ptr(), C.byref(pod), C.byref(res), out.counters.data_ptr(), int(splits)))
+    return out
+
+
+def _optimize_gd(x: torch.Tensor, cost: "JitModel", options: Options, history: bool, ctx: Context, out: Optional[Output],
+                 splits: Optional[int], zero_counters: bool) -> Output:
+    """gd::Optimizer (optimizers/gd.h) on a scalar cost model: one launch of toa_jit_gd_run.  No final Hessian (optimizer.h:313)."""
+    if options.has_host_controls():
+        raise ValueError("GradientDescent runs as one launch per solve: stop callbacks, max_duration_ms and the log line are not "
+                         "supported on this path (no stepping form for scalar costs)")
+    if splits is not None:
+        raise ValueError("GradientDescent: no row-split form (splits)")
+    from ._capi import ToaGdOptions
+    P = x.shape[0]
+    pod = options.to_pod()
+    gd = ToaGdOptions()
+    ctx.lib.toa_gd_options_default(C.byref(gd))
+    gd.lr = float(options.gd.lr)
+    if out is None:
+        import copy
+        o2 = copy.deepcopy(options)
+        o2.hessian.save_last = False
+        out = _alloc_output(P, cost.n, o2, history, x.device)
+    elif zero_counters:
+        out.counters.zero_()
+    res = _results_pod(out)
+    res.final_hessian = None
+    _apply_loss(ctx, cost)   # (a loss on a scalar cost is refused by the library)
+    check(ctx.lib.toa_jit_gd_run(ctx.h, cost.res._h, cost.items, P, cost.packed.data_ptr(), x.data_ptr(), C.byref(pod), C.byref(gd),
+                                 C.byref(res), out.counters.data_ptr()))
     return out
 
 
@@ -1090,6 +1142,10 @@ def accumulate(cost, x: torch.Tensor, want_grad: bool = True, ctx: Optional[Cont
     c = torch.zeros(P, dtype=torch.float64, device=dev)
     nres = torch.zeros(P, dtype=torch.int32, device=dev)
     _apply_loss(ctx, cost)
+    if isinstance(cost, JitModel) and cost.res.kind in JitResidual.COST_KINDS:   # SolverGD::Build: g and the cost, no H
+        check(ctx.lib.toa_jit_accumulate(ctx.h, cost.res._h, cost.items, P, cost.packed.data_ptr(), x.data_ptr(), int(want_grad),
+                                         g.data_ptr() if want_grad else None, None, c.data_ptr(), nres.data_ptr()))
+        return g, None, c, nres
     if isinstance(cost, JitModel):
         check(ctx.lib.toa_jit_accumulate(ctx.h, cost.res._h, cost.items, P, cost.packed.data_ptr(), x.data_ptr(), int(want_grad),
                                          g.data_ptr() if want_grad else None, H.data_ptr() if want_grad else None,

@@ -74,7 +74,7 @@ extern "C" {
 
 /* The DenseRow residual written as r(x) ONLY and differentiated on the device for wide parameter blocks (13 <= n <= 63,
  * "chunked Jets": the 16 lanes of a row group evaluate the functor on Jet chunks seeded on the columns each feeds to the
- * matrix cores; csrc/kernels.hpp JetRowModel).  Instantiated for n = 12 and n = 50 (BASELINE shapes C3 / C4);
+ * matrix cores; csrc/row_model.hpp, models_jet.hpp).  Instantiated for n = 12 and n = 50 (BASELINE shapes C3 / C4);
  * data_dev: [P][m][n + 1] = (a_i, b_i) rows in natural layout; x: [P][n]. */
 #define TOA_MODEL_DENSE_ROW_AD 11
 

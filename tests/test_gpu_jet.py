@@ -1,6 +1,6 @@
 """The device dual numbers (csrc/jet.hpp = ceres::Jet<T, N>, include/tinyopt/3rdparty/ceres/jet.h:216-1400) function
 by function: value and both partial derivatives through Jet<T, 2> against closed forms (numpy / scipy), like the
-reference's own derivative checks; and the wide-block AD model (JetRowModel, "chunked Jets") against the hand-derived
+reference's own derivative checks; and the wide-block AD model (RowModel over AdRowFunctor, row_model.hpp: "chunked Jets") against the hand-derived
 MFMA path and the oracle at the BASELINE shapes."""
 import ctypes as C
 

@@ -99,7 +99,7 @@ def test_the_memo_saves_the_pass_after_a_rejected_step(ta, oracle):
 
 
 def test_memo_with_device_ad_rows(ta, oracle):
-    """JetRowModel (device forward-mode AD in MFMA operand order) parks the same Gram registers."""
+    """RowModel over AdRowFunctor (row_model.hpp: device forward-mode AD, a row per lane) parks the same Gram registers."""
     P, n, m = 24, 12, 200
     A, b, x0, _ = oracle.synth_dense_row(P, n, m, np.float32, seed=3)
     model = ta.DenseRowAD(torch.from_numpy(A).cuda(), torch.from_numpy(b).cuda())

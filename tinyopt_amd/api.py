@@ -665,7 +665,7 @@ class DenseRowAD6(_LossMixin):
 
 class DenseRowAD:
     """The DenseRow residual for a WIDE parameter block written the tinyopt way — residual only, the Jacobian by device
-    AD in the matrix cores' operand layout (csrc/kernels.hpp JetRowModel, "chunked Jets").  n = 12 or n = 50.
+    AD in the matrix cores' operand layout (csrc/row_model.hpp RowModel over AdRowFunctor, "chunked Jets").  n = 12 or n = 50.
     A: [P, m, n], b: [P, m] (natural layout)."""
     model_id = MODEL_DENSE_ROW_AD
 

@@ -800,14 +800,7 @@ int launch_ba(toa_handle h, BaParams& prm) {
   if (lds > size_t(160 * 1024)) return toa_fail(TOA_E_UNSUPPORTED, "toa_ba_run: LDS footprint exceeds 160 KiB");
   const BaWork<T> wk(prm.C, prm.N, ROBUST);
   const size_t need = size_t(prm.P) * wk.total * sizeof(T);
-  if (need > h->scratch_bytes) {
-    if (int rc = grow_sync(h, "device workspace")) return rc;
-    toa_release_workspace(h, h->scratch);
-    h->scratch = nullptr;
-    h->scratch_bytes = 0;
-    HIP_TRY(hipMalloc(&h->scratch, need));
-    h->scratch_bytes = need;
-  }
+  if (int rc = ensure_workspace(h, &h->scratch, &h->scratch_bytes, need, "device workspace")) return rc;
   prm.work = h->scratch;
   static_assert(sizeof(BaParams) <= 1024, "parameter block too large");
   if (int rc = upload_params(h, &prm, sizeof(prm))) return rc;
@@ -1732,11 +1725,7 @@ int ba_lists_run_t(toa_handle h, int dtype, BlParams prm, double max_duration_ms
   // running at the end of it are finalised as kMaxIters, as the eager loop does.  Like the n > 128 pipeline's captured form this needs
   // a bounded budget (max_consec_failures > 0), every stage a kernel of this library (use_ldlt, the one-workgroup factorisations) and
   // workspaces that exist (a first eager call of the shape makes them); max_duration_ms needs the host's clock and is refused.
-  bool capturing = false;
-  {
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    capturing = hipStreamIsCapturing(h->stream, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone;
-  }
+  const bool capturing = stream_is_capturing(h->stream);
   const int C = prm.C, N = prm.N, M = prm.M, n = 6 * C;
   const long long P = prm.P;
   const BlWork<T> wk(C, N, M);
@@ -1764,14 +1753,8 @@ int ba_lists_run_t(toa_handle h, int dtype, BlParams prm, double max_duration_ms
   const int split = (C <= 128 && M / std::max(C, 1) >= 256) ? 3 : 1;   // (round 5, four scenes x 64 cameras, it/s: 2: 6759, 3: 7001, 4: 6730, 5: 6701, 6: 6865, 8: 6764; round 4, 8 against 4: 5.02 / 5.10 ms at four scenes, 10.43 / 10.28 at 32)
   const size_t b_sp = split > 1 ? al(size_t(P) * C * split * C * 36 * sizeof(T)) : 0, b_rp = split > 1 ? al(size_t(P) * C * split * 6 * sizeof(T)) : 0;
   const size_t need = b_work + b_iwork + b_ok + 256 + b_S + 2 * b_v + b_sp + b_rp;
-  if (need > h->aux_bytes) {   // (h->scratch belongs to toa_large_solve, which this pipeline calls)
-    if (int rc = grow_sync(h, "bundle adjustment workspace")) return rc;   // (refused under capture with a message that says why)
-    toa_release_workspace(h, h->aux);
-    h->aux = nullptr;
-    h->aux_bytes = 0;
-    HIP_TRY(hipMalloc(&h->aux, need));
-    h->aux_bytes = need;
-  }
+  // (h->scratch belongs to toa_large_solve, which this pipeline calls; a growth under capture is refused with a message that says why)
+  if (int rc = ensure_workspace(h, &h->aux, &h->aux_bytes, need, "bundle adjustment workspace")) return rc;
   char* base = static_cast<char*>(h->aux);
   prm.work = base;
   prm.iwork = reinterpret_cast<int*>(base + b_work);
@@ -1916,13 +1899,8 @@ extern "C" int toa_ba_run(toa_handle h, int dtype, int num_cameras, int num_poin
   if (num_cameras < 1 || num_cameras > 10) return toa_fail(TOA_E_ARG, "toa_ba_run: 1 <= num_cameras <= 10 (reduced camera system of one wavefront)");
   if (num_points < 1 || num_points > (1 << 22)) return toa_fail(TOA_E_ARG, "toa_ba_run: num_points out of range");
   if (P < 0 || P > 65535) return toa_fail(TOA_E_ARG, "toa_ba_run: P must be in [0, 65535]");
-  if (!data_dev || !x_dev || !options || !results) return toa_fail(TOA_E_ARG, "toa_ba_run: null pointer");
-  if (!results->stop_reason || !results->num_iters || !results->final_cost)
-    return toa_fail(TOA_E_ARG, "toa_ba_run: stop_reason, num_iters and final_cost outputs are required");
-  if (options->solver_type != 0 && options->solver_type != 1) return toa_fail(TOA_E_ARG, "toa_ba_run: solver_type must be 0 (LM) or 1 (GN)");
-  if ((results->errs || results->deltas2 || results->successes) && results->hist_stride < options->max_iters + 2)
-    return toa_fail(TOA_E_ARG, "toa_ba_run: hist_stride must be >= max_iters + 2");
-  if (options->max_iters < 0 || options->max_iters > 65535) return toa_fail(TOA_E_ARG, "max_iters out of range");
+  if (!data_dev || !x_dev || !results) return toa_fail(TOA_E_ARG, "toa_ba_run: null pointer");
+  if (int rc = check_run_args("toa_ba_run", options, results, 0, 1, kLmOrGn)) return rc;
   if (P == 0) return TOA_OK;
   TOA_ON_DEVICE(h->device);
   BaParams prm;
@@ -1945,13 +1923,8 @@ extern "C" int toa_ba_lists_run(toa_handle h, int dtype, int num_cameras, int nu
   if (num_cameras < 1 || num_cameras > 682) return toa_fail(TOA_E_ARG, "toa_ba_lists_run: 1 <= num_cameras <= 682 (reduced camera system of at most 4092 unknowns)");
   if (num_points < 1 || num_points > (1 << 22) || num_obs < 1 || num_obs > (1 << 26)) return toa_fail(TOA_E_ARG, "toa_ba_lists_run: num_points / num_obs out of range");
   if (P < 0 || P > 65535) return toa_fail(TOA_E_ARG, "toa_ba_lists_run: P must be in [0, 65535]");
-  if (!intr_dev || !obs_cam_dev || !obs_pt_dev || !obs_uv_dev || !x_dev || !options || !results) return toa_fail(TOA_E_ARG, "toa_ba_lists_run: null pointer");
-  if (!results->stop_reason || !results->num_iters || !results->final_cost)
-    return toa_fail(TOA_E_ARG, "toa_ba_lists_run: stop_reason, num_iters and final_cost outputs are required");
-  if (options->solver_type != 0 && options->solver_type != 1) return toa_fail(TOA_E_ARG, "toa_ba_lists_run: solver_type must be 0 (LM) or 1 (GN)");
-  if ((results->errs || results->deltas2 || results->successes) && results->hist_stride < options->max_iters + 2)
-    return toa_fail(TOA_E_ARG, "toa_ba_lists_run: hist_stride must be >= max_iters + 2");
-  if (options->max_iters < 0 || options->max_iters > 65535) return toa_fail(TOA_E_ARG, "max_iters out of range");
+  if (!intr_dev || !obs_cam_dev || !obs_pt_dev || !obs_uv_dev || !x_dev || !results) return toa_fail(TOA_E_ARG, "toa_ba_lists_run: null pointer");
+  if (int rc = check_run_args("toa_ba_lists_run", options, results, 0, 1, kLmOrGn)) return rc;
   if (P == 0) return TOA_OK;
   TOA_ON_DEVICE(h->device);
   BlParams prm;

@@ -209,7 +209,7 @@ static bool dense_row_lane_route(int dtag, int n, bool robust) {
   if (n >= 1 && n <= (dtag == 0 ? 11 : 5)) return true;      // narrow blocks, with or without an M-estimator
   if (dtag == 1 && n == 6) return true;                      // (fp64 n = 6: JetModel without the estimator branch for L2, RowModel with a loss)
   if (!robust) return false;
-  return n == 12 || n == 50 || (dtag == 1 && n == 6);         // the BASELINE shapes with an M-estimator on the handle
+  return n == 12 || n == 50;                                  // the BASELINE shapes with an M-estimator on the handle
 }
 int toa_inst_narrow_accumulate_0_0(toa_handle h, int n, int m, int64_t P, const void* data, const void* x, int want_grad, void* g, void* H, double* cost, int32_t* nres);
 int toa_inst_jetrow_fused_0_0(int n, toa_handle h, const toa::FusedParams& prm);
@@ -778,14 +778,8 @@ static int lm_run_impl(toa_handle h, int model, int dtype, int n, int m, int64_t
     if (int rc = check_model(model, n, m, data)) return rc;
   }
   if (int rc = check_loss_supported(h, model, "toa_lm_run")) return rc;
-  if (!x || !options || !results) return fail(TOA_E_ARG, "toa_lm_run: null pointer");
-  if (!results->stop_reason || !results->num_iters || !results->final_cost)
-    return fail(TOA_E_ARG, "toa_lm_run: stop_reason, num_iters and final_cost outputs are required");
-  if (options->solver_type != 0 && options->solver_type != 1)
-    return fail(TOA_E_ARG, "toa_lm_run: solver_type must be 0 (LM) or 1 (GN) on this path");  // optimize.h:75
-  if ((results->errs || results->deltas2 || results->successes) && results->hist_stride < options->max_iters + 2)
-    return fail(TOA_E_ARG, "toa_lm_run: hist_stride must be >= max_iters + 2");
-  if (options->max_iters < 0 || options->max_iters > 65535) return fail(TOA_E_ARG, "max_iters out of range");
+  if (!x || !results) return fail(TOA_E_ARG, "toa_lm_run: null pointer");
+  if (int rc = check_run_args("toa_lm_run", options, results, 0, 1, "0 (LM) or 1 (GN) on this path")) return rc;  // optimize.h:75
   if (P == 0) return TOA_OK;
   TOA_ON_DEVICE(h->device);
   if (natural) {

@@ -4,6 +4,7 @@
 #ifdef __HIPCC_RTC__
 #error "host_launch.hpp is host code: run-time builds include kernels.hpp, which leaves it out"
 #endif
+#include <algorithm>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -108,18 +109,64 @@ inline void toa_release_workspace(toa_context* h, void* block) {
   else (void)hipFree(block);
 }
 
+inline bool stream_is_capturing(hipStream_t stream) {
+  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+  return hipStreamIsCapturing(stream, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone;
+}
+
+// Make a workspace block of the handle (scratch / memo / aux, with its recorded size) hold at least `need` bytes.
 // Before a device workspace is re-allocated: everything queued on the stream may still use the old block, so the stream is
 // drained first — which, like the hipMalloc that follows, cannot happen while the stream is being CAPTURED into a hipGraph.
 // Workspaces only ever grow and are kept, so one un-captured call of the same shape beforehand is all a capturing caller
 // needs; without it the call is refused here instead of failing inside the runtime with the capture invalidated.
-inline int grow_sync(toa_context* h, const char* what) {
-  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-  if (hipStreamIsCapturing(h->stream, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone)
+inline int ensure_workspace(toa_context* h, void** block, size_t* bytes, size_t need, const char* what) {
+  if (need <= *bytes) return TOA_OK;
+  if (stream_is_capturing(h->stream))
     return toa_fail(TOA_E_UNSUPPORTED, std::string(what) + ": a device workspace has to grow, which cannot happen while the stream is being captured; "
                                        "run this shape once before hipStreamBeginCapture (workspaces only grow and are kept by the handle)");
   HIP_TRY(hipStreamSynchronize(h->stream));
+  toa_release_workspace(h, *block);
+  *block = nullptr;
+  *bytes = 0;
+  if (hipMalloc(block, need) != hipSuccess) {
+    (void)hipGetLastError();
+    return toa_fail(TOA_E_NOMEM, std::string(what) + ": cannot allocate " + std::to_string(need >> 20) + " MiB of device workspace");
+  }
+  *bytes = need;
   return TOA_OK;
 }
+
+// "Is this run well-formed", shared by every run entry point (`who` prefixes the messages): the required outputs, the solver types
+// the entry serves (`allowed`: how its message names them), the history stride and the iteration bound (not for a stepping
+// form whose loop the host drives: iters_capped = false).  Shape limits and data pointers are the caller's.
+inline int check_run_args(const char* who, const toa_options* options, const toa_results* results, int solver_lo, int solver_hi,
+                          const char* allowed, bool iters_capped = true) {
+  if (!options) return toa_fail(TOA_E_ARG, std::string(who) + ": null pointer");
+  if (!results->stop_reason || !results->num_iters || !results->final_cost)
+    return toa_fail(TOA_E_ARG, std::string(who) + ": stop_reason, num_iters and final_cost outputs are required");
+  if (options->solver_type < solver_lo || options->solver_type > solver_hi)
+    return toa_fail(TOA_E_ARG, std::string(who) + ": solver_type must be " + allowed);
+  if ((results->errs || results->deltas2 || results->successes) && results->hist_stride < options->max_iters + 2)
+    return toa_fail(TOA_E_ARG, std::string(who) + ": hist_stride must be >= max_iters + 2");
+  if (iters_capped && (options->max_iters < 0 || options->max_iters > 65535)) return toa_fail(TOA_E_ARG, "max_iters out of range");
+  return TOA_OK;
+}
+constexpr const char* kLmOrGn = "0 (LM) or 1 (GN)";
+
+// The queue block of the persistent kernels — [0] pop counter, [16] waves that have left: zeroed when the handle is created and
+// by the last wave of every launch; a launch that failed may have left them dirty, so the next one starts from a memset again.
+inline int reset_queue_if_dirty(toa_context* h) {
+  if (!h->queue_dirty) return TOA_OK;
+  HIP_TRY(hipMemsetAsync(h->queue, 0, 48 * sizeof(int), h->stream));
+  h->queue_dirty = false;
+  return TOA_OK;
+}
+// Grid of a persistent kernel: every resident workgroup, or as many as the batch has work for (may be 0 for an empty batch).
+inline long long persistent_grid(const toa_context* h, int wg_per_cu, long long P, int problems_per_wg) {
+  return std::min((long long)h->num_cus * wg_per_cu, (P + problems_per_wg - 1) / problems_per_wg);
+}
+// Grid of the one-pass kernels (a wave per problem, four per workgroup, grid-strided beyond eight workgroups per compute unit).
+inline long long accumulate_grid(const toa_context* h, long long P) { return std::min((P + 3) / 4, (long long)h->num_cus * 8); }
 
 namespace toa {
 // Every C entry point runs on its handle's GPU and leaves the CALLER's current device as it found it: torch (and any
@@ -167,8 +214,7 @@ inline int upload_params(toa_handle h, const void* blk, size_t bytes) {
   // launched, long after the caller's stack copy is gone — so the block is parked in host memory the handle keeps for its
   // lifetime (1 KB per captured launch).  And once a graph of ours exists, a replay can rewrite the device block behind the
   // shadow's back at any time: from then on every eager call uploads (~10 us), the shadow is retired for this handle.
-  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-  if (hipStreamIsCapturing(h->stream, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone) {
+  if (stream_is_capturing(h->stream)) {
     h->captured_blocks.emplace_back(new char[bytes]);
     std::memcpy(h->captured_blocks.back().get(), blk, bytes);
     HIP_TRY(hipMemcpyAsync(h->params_dev, h->captured_blocks.back().get(), bytes, hipMemcpyHostToDevice, h->stream));
@@ -232,9 +278,7 @@ template <typename Model>
 inline int launch_accumulate(toa_handle h, int n, int m, int64_t P, const void* data, const void* x, int want_grad,
                              void* g, void* H, double* cost, int32_t* nres) {
   using T = typename Model::Scalar;
-  long long grid = (P + 3) / 4;
-  const long long cap = (long long)h->num_cus * 8;
-  if (grid > cap) grid = cap;
+  const long long grid = accumulate_grid(h, P);
   size_t pw, pwg;
   if (int rc = lds_fit<T>(h, n, &pw, &pwg, 4, ModelStageBytes<Model>::value)) return rc;
   using RModel = typename RobustOf<Model>::type;
@@ -261,12 +305,7 @@ inline int launch_fused(toa_handle h, const FusedParams& prm_in) {
   if (int rc = lds_fit<T>(h, prm.n, &pw, &pwg, kW)) return rc;
   prm.lds_per_wave = (int)pw;
   prm.queue = h->queue;
-  // [0] pop counter, [16] waves that have left: zeroed when the handle is created and by the last wave of every launch
-  // (lm_fused_kernel); a launch that failed may have left them dirty, so the next one starts from a memset again
-  if (h->queue_dirty) {
-    HIP_TRY(hipMemsetAsync(h->queue, 0, 48 * sizeof(int), h->stream));
-    h->queue_dirty = false;
-  }
+  if (int rc = reset_queue_if_dirty(h)) return rc;
   auto kern = lm_fused_kernel<Model>;
   // resident workgroups per CU for a dynamic-LDS size (cached: the two HIP calls cost milliseconds)
   auto occupancy = [&](size_t lds_bytes, int* out) -> int {
@@ -364,9 +403,7 @@ inline int launch_fused(toa_handle h, const FusedParams& prm_in) {
       coop_chunking<Model>(h, prm.n, prm.m, &prm.coop_K, &prm.coop_cs);
     }
   }
-  long long grid = (long long)h->num_cus * wg_per_cu;
-  const long long need = (prm.P + NO - 1) / NO;
-  if (grid > need) grid = need;
+  long long grid = persistent_grid(h, wg_per_cu, prm.P, NO);
   if (grid < 1) grid = 1;
   // (Sizing the grid to P / rounds waves so that every round is full was tried: at the BASELINE shard size 625 workgroups
   // instead of 768 are ~2 % slower, tools/grid_ab.sh — more resident waves hide more latency than full rounds save.)
@@ -375,14 +412,7 @@ inline int launch_fused(toa_handle h, const FusedParams& prm_in) {
     if (memo_on && prm.memo_lds_off == 0) {
       const size_t stride = (Model::kMemoBytes + 255) & ~size_t(255);
       const size_t need_b = stride * size_t(grid) * NO;
-      if (need_b > h->memo_bytes) {
-        if (int rc = grow_sync(h, "memo of the last accepted linearisation")) return rc;
-        toa_release_workspace(h, h->memo);
-        h->memo = nullptr;
-        h->memo_bytes = 0;
-        HIP_TRY(hipMalloc(&h->memo, need_b));
-        h->memo_bytes = need_b;
-      }
+      if (int rc = ensure_workspace(h, &h->memo, &h->memo_bytes, need_b, "memo of the last accepted linearisation")) return rc;
       prm.memo = h->memo;
       prm.memo_stride = stride;
     }
@@ -511,14 +541,7 @@ inline int launch_wide(toa_handle h, const FusedParams& fp, int splits_req) {
   const size_t b_hsum = (size_t(P) * n * n * sizeof(T) + 255) & ~size_t(255);
   const size_t b_sync = (size_t(2 * P + 1) * sizeof(unsigned) + 255) & ~size_t(255);
   const size_t need = b_state + b_part + b_hsum + b_sync;
-  if (need > h->scratch_bytes) {
-    if (int rc = grow_sync(h, "device workspace")) return rc;
-    toa_release_workspace(h, h->scratch);
-    h->scratch = nullptr;
-    h->scratch_bytes = 0;
-    HIP_TRY(hipMalloc(&h->scratch, need));
-    h->scratch_bytes = need;
-  }
+  if (int rc = ensure_workspace(h, &h->scratch, &h->scratch_bytes, need, "device workspace")) return rc;
   WideParams wp;
   std::memset(&wp, 0, sizeof(wp));
   wp.data = fp.data; wp.x = fp.x; wp.P = P; wp.n = n; wp.m = m;
@@ -637,9 +660,7 @@ inline int launch_wide(toa_handle h, const FusedParams& fp, int splits_req) {
 
 template <typename T, int NPAD>
 inline int launch_solve(toa_handle h, int n, int64_t P, const void* H, const void* g, double scale, void* dx, int32_t* ok) {
-  long long grid = (P + 3) / 4;
-  const long long cap = (long long)h->num_cus * 8;
-  if (grid > cap) grid = cap;
+  const long long grid = accumulate_grid(h, P);
   size_t pw, pwg;
   if (int rc = lds_fit<T>(h, n, &pw, &pwg)) return rc;
   if (int rc = ensure_lds_attr(h, (const void*)solve_damped_kernel<T, NPAD>, pwg)) return rc;
@@ -650,9 +671,7 @@ inline int launch_solve(toa_handle h, int n, int64_t P, const void* H, const voi
 }
 template <typename T, int NPAD>
 inline int launch_inv_cov(toa_handle h, int n, int64_t P, const void* H, void* C, int32_t* ok) {
-  long long grid = (P + 3) / 4;
-  const long long cap = (long long)h->num_cus * 8;
-  if (grid > cap) grid = cap;
+  const long long grid = accumulate_grid(h, P);
   size_t pw, pwg;
   if (int rc = lds_fit<T>(h, n, &pw, &pwg)) return rc;
   if (int rc = ensure_lds_attr(h, (const void*)inv_cov_kernel<T, NPAD>, pwg)) return rc;

@@ -5,7 +5,7 @@
 // Same algebra, same formulas (each operator cites the reference line it restates); what differs is the
 // storage: the infinitesimal part is a plain T[N] that lives in VGPRs (N is a compile-time constant; the
 // reference's N = Dynamic heap vectors have no place in a kernel — wide parameter blocks are differentiated
-// in chunks instead, JetRowModel in kernels.hpp).  With it a user writes only
+// in chunks instead, AdRowFunctor in row_model.hpp).  With it a user writes only
 // `r(x)` as a template over the scalar type, exactly like a tinyopt residual functor, and JetModel
 // (kernels.hpp) turns it into the Accumulate contract on the device.
 #pragma once

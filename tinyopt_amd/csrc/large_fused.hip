@@ -771,14 +771,7 @@ int launch_large_accumulate(toa_handle h, int n, int m, int64_t P, const T* data
   long long grid = std::min<long long>(P, (long long)h->num_cus * 2);
   const size_t per_wg = (size_t(4) * NT * 64 * sizeof(Acc) + 255) & ~size_t(255);
   const size_t need = per_wg * size_t(grid);
-  if (need > h->scratch_bytes) {
-    if (int rc = grow_sync(h, "device workspace")) return rc;
-    toa_release_workspace(h, h->scratch);
-    h->scratch = nullptr;
-    h->scratch_bytes = 0;
-    HIP_TRY(hipMalloc(&h->scratch, need));
-    h->scratch_bytes = need;
-  }
+  if (int rc = ensure_workspace(h, &h->scratch, &h->scratch_bytes, need, "device workspace")) return rc;
   hipLaunchKernelGGL((large_accumulate_kernel<T, NB>), dim3((unsigned)grid), dim3(256), 0, h->stream, data, x, n, m, (long long)P,
                      want_grad, g, H, cost, nres, static_cast<char*>(h->scratch), per_wg);
   HIP_TRY(hipGetLastError());
@@ -816,24 +809,13 @@ int launch_large_fused_r(toa_handle h, int n, int m, int64_t P, const T* data, T
     if (wg_per_cu < 1) return toa_fail(TOA_E_UNSUPPORTED, "large-n fused kernel does not fit this device");
     if (h->ncfg < 256) h->cfg[h->ncfg++] = {(const void*)kern, lds, wg_per_cu};
   }
-  long long grid = (long long)h->num_cus * wg_per_cu;
-  if (grid > P) grid = P;
+  const long long grid = persistent_grid(h, wg_per_cu, P, 1);
   if (grid < 1) return TOA_OK;
   // 4 partial Grams + two H slots (the current linearisation and the parked one) + four vectors (undamped diagonal; memo: g, diagonal, x)
   const size_t per_wg = ((size_t(4) * NT * 64 * sizeof(Acc) + (size_t(2) * n * n + size_t(4) * 16 * NB) * sizeof(T)) + 255) & ~size_t(255);
   const size_t need = per_wg * size_t(grid);
-  if (need > h->scratch_bytes) {
-    if (int rc = grow_sync(h, "device workspace")) return rc;
-    toa_release_workspace(h, h->scratch);
-    h->scratch = nullptr;
-    h->scratch_bytes = 0;
-    HIP_TRY(hipMalloc(&h->scratch, need));
-    h->scratch_bytes = need;
-  }
-  if (h->queue_dirty) {
-    HIP_TRY(hipMemsetAsync(h->queue, 0, 48 * sizeof(int), h->stream));
-    h->queue_dirty = false;
-  }
+  if (int rc = ensure_workspace(h, &h->scratch, &h->scratch_bytes, need, "device workspace")) return rc;
+  if (int rc = reset_queue_if_dirty(h)) return rc;
   LfArgs<T> a;
   a.data = data; a.x = x; a.n = n; a.m = m; a.P = P; a.opt = opt; a.res = res;
   a.queue = h->queue;

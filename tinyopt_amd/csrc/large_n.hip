@@ -99,17 +99,7 @@ int ensure_scratch(toa_handle h, size_t need, const char* what) {
   // toa_tuning::fail_workspace_alloc: a test hook — the request fails as on an exhausted device
   if (h->tune.fail_workspace_alloc)
     return toa_fail(TOA_E_NOMEM, std::string(what) + ": cannot allocate " + std::to_string(need >> 20) + " MiB of device workspace (toa_tuning::fail_workspace_alloc)");
-  if (need <= h->scratch_bytes) return TOA_OK;
-  if (int rc = grow_sync(h, what)) return rc;
-  toa_release_workspace(h, h->scratch);
-  h->scratch = nullptr;
-  h->scratch_bytes = 0;
-  if (hipMalloc(&h->scratch, need) != hipSuccess) {
-    (void)hipGetLastError();
-    return toa_fail(TOA_E_NOMEM, std::string(what) + ": cannot allocate " + std::to_string(need >> 20) + " MiB of device workspace");
-  }
-  h->scratch_bytes = need;
-  return TOA_OK;
+  return ensure_workspace(h, &h->scratch, &h->scratch_bytes, need, what);
 }
 
 // The context's rocBLAS handle (created on first use), bound to the context's stream.
@@ -2248,8 +2238,7 @@ int large_lm_run_t(toa_handle h, int n, int m, int64_t P, const T* data, T* x, c
   // solve with no host in the loop (one lane: a captured fork / join would only add edges).  A typical solve needs a fifth of
   // the budget; the rest costs ~40 us of empty launches per pass.  With a library stage in the pass there is no such form.
   {
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(st, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone) {
+    if (stream_is_capturing(st)) {
       if (!ahead)
         return toa_fail(TOA_E_UNSUPPORTED, "large-n LM under stream capture: only the solves whose every stage is a kernel of this library "
                                            "(fp32, 16-byte aligned rows, use_ldlt, n <= 1024, not the stepping form) can be captured");

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Throughput of device AD against the hand-derived MFMA path on the same problems: the DenseRow residual
-written as r(x) only (TOA_MODEL_DENSE_ROW_AD, JetRowModel: chunked Jets in the MFMA operand layout) vs DenseRowModel."""
+written as r(x) only (TOA_MODEL_DENSE_ROW_AD, RowModel over AdRowFunctor, csrc/row_model.hpp: chunked Jets, a row per lane) vs DenseRowModel."""
 import os
 import sys
 

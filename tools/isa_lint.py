@@ -149,7 +149,7 @@ def lint_object(obj):
         local = os.path.join(td, os.path.basename(obj))
         with open(obj, "rb") as f, open(local, "wb") as g:
             g.write(f.read())
-        if obj.endswith(".co"):   # a bare gfx950 code object (e.g. one taken out of the run-time compiler's cache, tools/jit_lint.py)
+        if obj.endswith(".co"):   # a bare gfx950 code object (e.g. one taken out of the run-time compiler's cache)
             cos = [local]
         else:
             subprocess.run([f"{LLVM}/llvm-objdump", "--offloading", local], cwd=td, check=True, capture_output=True)

@@ -593,6 +593,32 @@ def test_two_lanes_give_the_bits_of_one_lane(ta, oracle, P, n, m):
     assert int(outs[0][1].num_iters.max()) > int(outs[0][1].num_iters.min())
 
 
+def test_two_lanes_with_a_loss_give_the_bits_of_one_lane(ta, oracle):
+    """The same with an M-estimator, histories and the final Hessian: P = 17 splits into unequal lanes of 8 and 9 (two lanes need
+    P >= 16), n = 132 is the smallest fp32 shape on the own-kernel route beyond 128 (n % 4 == 0, m (n + 1) % 4 == 0) — the lane
+    shift of the loss arrays (lossv, ninl), of the memo arrays and of every results pointer is in play at once."""
+    P, n, m = 17, 132, 264
+    A, b, x0, _ = oracle.synth_dense_row(P, n, m, np.float32, seed=n + P)
+    A[3, :, 5] = 0.0   # one problem that fails its solves: the lanes finish at different passes
+    model = ta.DenseRowNatural(torch.from_numpy(A).cuda(), torch.from_numpy(b).cuda()).with_loss("huber", 0.5)
+    opts = ta.Options()
+    opts.hessian.save_last = True
+    ctx = ta.api.default_context()
+    outs = []
+    for one_lane in (1, 2):
+        x = torch.from_numpy(x0.copy()).cuda()
+        with ctx.tuning(large_one_lane=one_lane):
+            out = ta.Optimize(x, model, opts, history=True)
+        torch.cuda.synchronize()
+        outs.append((x, out))
+    (x1, o1), (x2, o2) = outs
+    assert torch.equal(x2, x1)
+    assert o1.final_hessian is not None
+    for f in ("stop_reason", "num_iters", "final_cost", "num_failures", "errs", "deltas2", "successes", "final_hessian"):
+        assert torch.equal(getattr(o2, f), getattr(o1, f)), f
+    assert torch.equal(o2.counters[:4], o1.counters[:4])
+
+
 def test_a_few_huge_problems_take_the_row_split_pipeline(ta, oracle):
     """64 <= n <= 128 with ONE (or a handful of) problems of tens of thousands of rows: a workgroup per problem would use one
     compute unit, so toa_lm_run routes such a batch to the launch-per-stage pipeline, whose rows kernel and Gram split every

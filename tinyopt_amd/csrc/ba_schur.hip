@@ -19,6 +19,7 @@
 //   data: [f cx cy 0 0 0 0 0 | uv: C x N x 2 | vis: C x N]     x: [12 C poses (R row-major, t) | 3 N points], in place
 #include "kernels.hpp"
 #include "ldlt_wg.hpp"
+#include "large_route.hpp"
 
 namespace toa {
 
@@ -1736,9 +1737,8 @@ int ba_lists_run_t(toa_handle h, int dtype, BlParams prm, double max_duration_ms
     constexpr long long kMaxCapturedPasses = 256;
     const long long tries = prm.opt.max_consec_failures > 0 ? (long long)prm.opt.max_consec_failures + 1 : 256;
     max_passes = (long long)(prm.opt.max_iters + 2) * tries;
-    const size_t chol2_lds = (size_t(32) * 36 + size_t(n) * 37 + 96) * sizeof(T) + 64;
-    const bool own_solver = n <= 128 || (P <= 65535 && chol2_lds + 2048 <= size_t(h->max_lds));
-    if (max_duration_ms > 0 || !prm.opt.use_ldlt || h->tune.large_library_solver != 0 || !own_solver)
+    const bool own_solver = large_route(size_t(h->max_lds), h->tune.large_library_solver != 0, sizeof(T), n, P, prm.opt.use_ldlt).route != LargeRoute::Library;
+    if (max_duration_ms > 0 || !own_solver)
       return toa_fail(TOA_E_UNSUPPORTED, "toa_ba_lists_run under stream capture: only solves whose every stage is a kernel of this library can be captured "
                                          "(use_ldlt, the one-workgroup factorisation of the reduced camera system, no max_duration_ms)");
     if (max_passes > kMaxCapturedPasses)

@@ -153,6 +153,18 @@ inline int check_run_args(const char* who, const toa_options* options, const toa
 }
 constexpr const char* kLmOrGn = "0 (LM) or 1 (GN)";
 
+// The results block of a batch as seen from its problem p0 (a slice or a lane of the batch): every output that is there, moved on by
+// p0 rows of its own stride.  n: the unknowns per problem (final_hessian is [P][n][n]).
+inline toa_results results_at(const toa_results& res, int64_t p0, int n) {
+  toa_results r = res;
+  auto adv = [&](auto*& ptr, size_t per) { if (ptr) ptr += size_t(p0) * per; };
+  adv(r.stop_reason, 1); adv(r.num_iters, 1); adv(r.num_failures, 1); adv(r.num_consec_failures, 1);
+  adv(r.final_cost, 1); adv(r.final_num_residuals, 1); adv(r.final_rerr_dec, 1); adv(r.final_hessian, size_t(n) * n);
+  adv(r.errs, size_t(r.hist_stride)); adv(r.deltas2, size_t(r.hist_stride)); adv(r.successes, size_t(r.hist_stride));
+  adv(r.final_inlier_ratio, 1);
+  return r;
+}
+
 // The queue block of the persistent kernels — [0] pop counter, [16] waves that have left: zeroed when the handle is created and
 // by the last wave of every launch; a launch that failed may have left them dirty, so the next one starts from a memset again.
 inline int reset_queue_if_dirty(toa_context* h) {

@@ -18,6 +18,7 @@
 #include "kernels.hpp"
 #include "ldlt_wg.hpp"
 #include "chol_diag.hpp"
+#include "large_route.hpp"
 
 namespace toa {
 namespace {
@@ -39,10 +40,6 @@ struct RocApi {
   int (*sgetrs)(rb_handle, int, int, int, float*, int, int64_t, const int*, int64_t, float*, int, int64_t, int) = nullptr;
   int (*dgetrs)(rb_handle, int, int, int, double*, int, int64_t, const int*, int64_t, double*, int, int64_t, int) = nullptr;
   int (*dpotrs)(rb_handle, int, int, int, double*, int, int64_t, double*, int, int64_t, int) = nullptr;
-  int (*sgemm)(rb_handle, int, int, int, int, int, const float*, const float*, int, int64_t, const float*, int, int64_t,
-               const float*, float*, int, int64_t, int) = nullptr;
-  int (*dgemm)(rb_handle, int, int, int, int, int, const double*, const double*, int, int64_t, const double*, int, int64_t,
-               const double*, double*, int, int64_t, int) = nullptr;
   int (*sgemm_b)(rb_handle, int, int, int, int, int, const float*, const float* const*, int, const float* const*, int, const float*,
                  float* const*, int, int) = nullptr;
   int (*dgemm_b)(rb_handle, int, int, int, int, int, const double*, const double* const*, int, const double* const*, int,
@@ -53,6 +50,13 @@ struct RocApi {
                const double*, double*, int, int64_t, int) = nullptr;
   std::string err;
   bool ok = false;
+  // the same calls by element type (arguments as of the s / d entry above)
+  template <typename T, typename... A> int potrf(A... a) const { if constexpr (sizeof(T) == 4) return spotrf(a...); else return dpotrf(a...); }
+  template <typename T, typename... A> int potrs(A... a) const { if constexpr (sizeof(T) == 4) return spotrs(a...); else return dpotrs(a...); }
+  template <typename T, typename... A> int getrf(A... a) const { if constexpr (sizeof(T) == 4) return sgetrf(a...); else return dgetrf(a...); }
+  template <typename T, typename... A> int getrs(A... a) const { if constexpr (sizeof(T) == 4) return sgetrs(a...); else return dgetrs(a...); }
+  template <typename T, typename... A> int gemm_batched(A... a) const { if constexpr (sizeof(T) == 4) return sgemm_b(a...); else return dgemm_b(a...); }
+  template <typename T, typename... A> int gemv(A... a) const { if constexpr (sizeof(T) == 4) return sgemv(a...); else return dgemv(a...); }
 };
 
 RocApi& roc_api() {
@@ -83,8 +87,6 @@ RocApi& roc_api() {
     api.dgetrf = reinterpret_cast<decltype(api.dgetrf)>(sym(sol, "rocsolver_dgetrf_strided_batched"));
     api.sgetrs = reinterpret_cast<decltype(api.sgetrs)>(sym(sol, "rocsolver_sgetrs_strided_batched"));
     api.dgetrs = reinterpret_cast<decltype(api.dgetrs)>(sym(sol, "rocsolver_dgetrs_strided_batched"));
-    api.sgemm = reinterpret_cast<decltype(api.sgemm)>(sym(blas, "rocblas_sgemm_strided_batched"));
-    api.dgemm = reinterpret_cast<decltype(api.dgemm)>(sym(blas, "rocblas_dgemm_strided_batched"));
     api.sgemm_b = reinterpret_cast<decltype(api.sgemm_b)>(sym(blas, "rocblas_sgemm_batched"));
     api.dgemm_b = reinterpret_cast<decltype(api.dgemm_b)>(sym(blas, "rocblas_dgemm_batched"));
     api.sgemv = reinterpret_cast<decltype(api.sgemv)>(sym(blas, "rocblas_sgemv_strided_batched"));
@@ -153,34 +155,51 @@ __global__ void __launch_bounds__(256) large_finish_kernel(const T* __restrict__
   if (threadIdx.x == 0) ok[p] = good ? 1 : 0;
 }
 
+// What the K3 seams below share: the scratch block carved into work [P][n][n] | rhs [P][n * rhs_cols] | info [P] | extra
+// [P][extra_ints] (pivots, flags), each 256-byte aligned; the copy with the damped diagonal in front of the factorisation
+// (large_damp_kernel) and the verdict behind it (large_finish_kernel).
+template <typename T>
+struct SolveScratch {
+  toa_handle h;
+  int n;
+  int64_t P;
+  T *work = nullptr, *rhs = nullptr;
+  int *info = nullptr, *extra = nullptr;
+  int64_t nn() const { return int64_t(n) * n; }
+  int carve(int rhs_cols = 1, size_t extra_ints = 0) {
+    auto al = [](size_t b) { return (b + 255) & ~size_t(255); };
+    const size_t b_work = al(size_t(P) * size_t(nn()) * sizeof(T)), b_rhs = al(size_t(P) * n * rhs_cols * sizeof(T));
+    const size_t b_info = al(size_t(P) * sizeof(int)), b_extra = al(size_t(P) * extra_ints * sizeof(int));
+    if (int rc = ensure_scratch(h, b_work + b_rhs + b_info + b_extra, "large-n solve")) return rc;
+    char* base = static_cast<char*>(h->scratch);
+    work = reinterpret_cast<T*>(base);
+    rhs = reinterpret_cast<T*>(base + b_work);
+    info = reinterpret_cast<int*>(base + b_work + b_rhs);
+    extra = reinterpret_cast<int*>(base + b_work + b_rhs + b_info);
+    return TOA_OK;
+  }
+  void damp(const T* H, const T* g, double scale) const {
+    const unsigned gx = unsigned(std::min<size_t>((size_t(nn()) + 255) / 256, 64));
+    hipLaunchKernelGGL(large_damp_kernel<T>, dim3(gx, unsigned(P)), dim3(256), 0, h->stream, H, g, work, rhs, n, scale);
+  }
+  int finish(T* dx, int32_t* ok, const int* active = nullptr) const {
+    hipLaunchKernelGGL(large_finish_kernel<T>, dim3(unsigned(P)), dim3(256), 0, h->stream, rhs, info, dx, ok, n, active);
+    HIP_TRY(hipGetLastError());
+    return TOA_OK;
+  }
+};
+
 template <typename T>
 int large_solve_t(toa_handle h, RocApi& api, int n, int64_t P, const T* H, const T* g, double scale, T* dx, int32_t* ok) {
-  const size_t nn = size_t(n) * n;
-  const size_t b_work = (size_t(P) * nn * sizeof(T) + 255) & ~size_t(255);
-  const size_t b_rhs = (size_t(P) * n * sizeof(T) + 255) & ~size_t(255);
-  const size_t b_info = (size_t(P) * sizeof(int) + 255) & ~size_t(255);
-  const size_t need = b_work + b_rhs + b_info;
-  if (int rc = ensure_scratch(h, need, "large-n solve")) return rc;
-  char* base = static_cast<char*>(h->scratch);
-  T* work = reinterpret_cast<T*>(base);
-  T* rhs = reinterpret_cast<T*>(base + b_work);
-  int* info = reinterpret_cast<int*>(base + b_work + b_rhs);
+  SolveScratch<T> s{h, n, P};
+  if (int rc = s.carve()) return rc;
   if (int rc = ensure_blas(h, api)) return rc;
-  const unsigned gx = unsigned(std::min<size_t>((nn + 255) / 256, 64));
-  hipLaunchKernelGGL(large_damp_kernel<T>, dim3(gx, unsigned(P)), dim3(256), 0, h->stream, H, g, work, rhs, n, scale);
+  s.damp(H, g, scale);
   HIP_TRY(hipGetLastError());
-  int rc;
-  if constexpr (sizeof(T) == 4) {
-    rc = api.spotrf(h->blas, kFillUpper, n, work, n, int64_t(nn), info, int(P));
-    if (rc == 0) rc = api.spotrs(h->blas, kFillUpper, n, 1, work, n, int64_t(nn), rhs, n, int64_t(n), int(P));
-  } else {
-    rc = api.dpotrf(h->blas, kFillUpper, n, work, n, int64_t(nn), info, int(P));
-    if (rc == 0) rc = api.dpotrs(h->blas, kFillUpper, n, 1, work, n, int64_t(nn), rhs, n, int64_t(n), int(P));
-  }
+  int rc = api.potrf<T>(h->blas, kFillUpper, n, s.work, n, s.nn(), s.info, int(P));
+  if (rc == 0) rc = api.potrs<T>(h->blas, kFillUpper, n, 1, s.work, n, s.nn(), s.rhs, n, int64_t(n), int(P));
   if (rc != 0) return toa_fail(TOA_E_HIP, "rocSOLVER potrf/potrs returned status " + std::to_string(rc));
-  hipLaunchKernelGGL(large_finish_kernel<T>, dim3(unsigned(P)), dim3(256), 0, h->stream, rhs, info, dx, ok, n);
-  HIP_TRY(hipGetLastError());
-  return TOA_OK;
+  return s.finish(dx, ok);
 }
 
 // dx = -H^-1 g "without any checks on invertibility" (gn.h:157-162, options.h:59: use_ldlt = false): a general LU with partial
@@ -188,36 +207,20 @@ int large_solve_t(toa_handle h, RocApi& api, int n, int64_t P, const T* H, const
 // everywhere else).  ONE matrix per call: a matrix solved alone gives the bits of its row in a batch.
 template <typename T>
 int large_solve_lu_t(toa_handle h, RocApi& api, int n, int64_t P, const T* H, const T* g, double scale, T* dx, int32_t* ok) {
-  const size_t nn = size_t(n) * n;
-  const size_t b_work = (size_t(P) * nn * sizeof(T) + 255) & ~size_t(255);
-  const size_t b_rhs = (size_t(P) * n * sizeof(T) + 255) & ~size_t(255);
-  const size_t b_info = (size_t(P) * sizeof(int) + 255) & ~size_t(255);
-  const size_t b_piv = (size_t(P) * n * sizeof(int) + 255) & ~size_t(255);
-  if (int rc = ensure_scratch(h, b_work + b_rhs + b_info + b_piv, "large-n solve")) return rc;
-  char* base = static_cast<char*>(h->scratch);
-  T* work = reinterpret_cast<T*>(base);
-  T* rhs = reinterpret_cast<T*>(base + b_work);
-  int* info = reinterpret_cast<int*>(base + b_work + b_rhs);
-  int* ipiv = reinterpret_cast<int*>(base + b_work + b_rhs + b_info);
+  SolveScratch<T> s{h, n, P};
+  if (int rc = s.carve(1, size_t(n))) return rc;
+  int* ipiv = s.extra;
   if (int rc = ensure_blas(h, api)) return rc;
-  const unsigned gx = unsigned(std::min<size_t>((nn + 255) / 256, 64));
-  hipLaunchKernelGGL(large_damp_kernel<T>, dim3(gx, unsigned(P)), dim3(256), 0, h->stream, H, g, work, rhs, n, scale);
+  s.damp(H, g, scale);
   HIP_TRY(hipGetLastError());
+  const int64_t nn = s.nn();
   for (int64_t p = 0; p < P; ++p) {
-    int rc;
-    if constexpr (sizeof(T) == 4) {
-      rc = api.sgetrf(h->blas, n, n, work + p * nn, n, int64_t(nn), ipiv + p * n, int64_t(n), info + p, 1);
-      if (rc == 0) rc = api.sgetrs(h->blas, kOpN, n, 1, work + p * nn, n, int64_t(nn), ipiv + p * n, int64_t(n), rhs + p * n, n, int64_t(n), 1);
-    } else {
-      rc = api.dgetrf(h->blas, n, n, work + p * nn, n, int64_t(nn), ipiv + p * n, int64_t(n), info + p, 1);
-      if (rc == 0) rc = api.dgetrs(h->blas, kOpN, n, 1, work + p * nn, n, int64_t(nn), ipiv + p * n, int64_t(n), rhs + p * n, n, int64_t(n), 1);
-    }
+    int rc = api.getrf<T>(h->blas, n, n, s.work + p * nn, n, nn, ipiv + p * n, int64_t(n), s.info + p, 1);
+    if (rc == 0) rc = api.getrs<T>(h->blas, kOpN, n, 1, s.work + p * nn, n, nn, ipiv + p * n, int64_t(n), s.rhs + p * n, n, int64_t(n), 1);
     if (rc != 0) return toa_fail(TOA_E_HIP, "rocSOLVER getrf/getrs returned status " + std::to_string(rc));
   }
-  HIP_TRY(hipMemsetAsync(info, 0, size_t(P) * sizeof(int), h->stream));   // unchecked: a singular pivot is not a failure by itself
-  hipLaunchKernelGGL(large_finish_kernel<T>, dim3(unsigned(P)), dim3(256), 0, h->stream, rhs, info, dx, ok, n);
-  HIP_TRY(hipGetLastError());
-  return TOA_OK;
+  HIP_TRY(hipMemsetAsync(s.info, 0, size_t(P) * sizeof(int), h->stream));   // unchecked: a singular pivot is not a failure by itself
+  return s.finish(dx, ok);
 }
 
 // The same solve with ONE matrix per library call — rocSOLVER's batched Cholesky picks its blocking from the batch size, and
@@ -227,15 +230,8 @@ int large_solve_lu_t(toa_handle h, RocApi& api, int n, int64_t P, const T* H, co
 // behind one another on the context's stream.  Fork / join by events; everything else stays on the context's stream.
 template <typename T>
 int large_solve_each_t(toa_handle h, RocApi& api, int n, int64_t P, const T* H, const T* g, double scale, T* dx, int32_t* ok) {
-  const size_t nn = size_t(n) * n;
-  const size_t b_work = (size_t(P) * nn * sizeof(T) + 255) & ~size_t(255);
-  const size_t b_rhs = (size_t(P) * n * sizeof(T) + 255) & ~size_t(255);
-  const size_t b_info = (size_t(P) * sizeof(int) + 255) & ~size_t(255);
-  if (int rc = ensure_scratch(h, b_work + b_rhs + b_info, "large-n solve")) return rc;
-  char* base = static_cast<char*>(h->scratch);
-  T* work = reinterpret_cast<T*>(base);
-  T* rhs = reinterpret_cast<T*>(base + b_work);
-  int* info = reinterpret_cast<int*>(base + b_work + b_rhs);
+  SolveScratch<T> s{h, n, P};
+  if (int rc = s.carve()) return rc;
   if (int rc = ensure_blas(h, api)) return rc;   // (also records how to destroy a handle)
   const int K = int(std::min<int64_t>(toa_context::kSide, P));
   while (h->nside < K) {
@@ -247,30 +243,23 @@ int large_solve_each_t(toa_handle h, RocApi& api, int n, int64_t P, const T* H, 
     h->nside = i + 1;
   }
   if (!h->side_fork) HIP_TRY(hipEventCreateWithFlags(&h->side_fork, hipEventDisableTiming));
-  const unsigned gx = unsigned(std::min<size_t>((nn + 255) / 256, 64));
-  hipLaunchKernelGGL(large_damp_kernel<T>, dim3(gx, unsigned(P)), dim3(256), 0, h->stream, H, g, work, rhs, n, scale);
+  s.damp(H, g, scale);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipEventRecord(h->side_fork, h->stream));
   for (int i = 0; i < K; ++i) HIP_TRY(hipStreamWaitEvent(h->side_stream[i], h->side_fork, 0));
+  const int64_t nn = s.nn();
   int rc = 0;
   for (int64_t q = 0; q < P && rc == 0; ++q) {
     void* hb = h->side_blas[q % K];
-    if constexpr (sizeof(T) == 4) {
-      rc = api.spotrf(hb, kFillUpper, n, work + q * nn, n, int64_t(nn), info + q, 1);
-      if (rc == 0) rc = api.spotrs(hb, kFillUpper, n, 1, work + q * nn, n, int64_t(nn), rhs + q * n, n, int64_t(n), 1);
-    } else {
-      rc = api.dpotrf(hb, kFillUpper, n, work + q * nn, n, int64_t(nn), info + q, 1);
-      if (rc == 0) rc = api.dpotrs(hb, kFillUpper, n, 1, work + q * nn, n, int64_t(nn), rhs + q * n, n, int64_t(n), 1);
-    }
+    rc = api.potrf<T>(hb, kFillUpper, n, s.work + q * nn, n, nn, s.info + q, 1);
+    if (rc == 0) rc = api.potrs<T>(hb, kFillUpper, n, 1, s.work + q * nn, n, nn, s.rhs + q * n, n, int64_t(n), 1);
   }
   for (int i = 0; i < K; ++i) {   // join (also after a failed call: nothing may still be running on the side when we return)
     HIP_TRY(hipEventRecord(h->side_done[i], h->side_stream[i]));
     HIP_TRY(hipStreamWaitEvent(h->stream, h->side_done[i], 0));
   }
   if (rc != 0) return toa_fail(TOA_E_HIP, "rocSOLVER potrf/potrs returned status " + std::to_string(rc));
-  hipLaunchKernelGGL(large_finish_kernel<T>, dim3(unsigned(P)), dim3(256), 0, h->stream, rhs, info, dx, ok, n);
-  HIP_TRY(hipGetLastError());
-  return TOA_OK;
+  return s.finish(dx, ok);
 }
 
 // C = H^-1 for n > 63 (tinyopt::InvCov, math.h:41-91): Cholesky against the identity.
@@ -294,27 +283,17 @@ __global__ void __launch_bounds__(256) large_inv_finish_kernel(T* __restrict__ C
 
 template <typename T>
 int large_inv_t(toa_handle h, RocApi& api, int n, int64_t P, const T* H, T* Cm, int32_t* ok) {
-  const size_t nn = size_t(n) * n;
-  const size_t b_work = (size_t(P) * nn * sizeof(T) + 255) & ~size_t(255);
-  const size_t b_info = (size_t(P) * sizeof(int) + 255) & ~size_t(255);
-  const size_t need = b_work + b_info;
-  if (int rc = ensure_scratch(h, need, "large-n solve")) return rc;
-  T* work = reinterpret_cast<T*>(h->scratch);
-  int* info = reinterpret_cast<int*>(static_cast<char*>(h->scratch) + b_work);
+  SolveScratch<T> s{h, n, P};
+  if (int rc = s.carve(0)) return rc;   // (the right-hand side is the caller's C, started as the identity: no rhs block)
   if (int rc = ensure_blas(h, api)) return rc;
-  HIP_TRY(hipMemcpyAsync(work, H, size_t(P) * nn * sizeof(T), hipMemcpyDeviceToDevice, h->stream));
-  const unsigned gx = unsigned(std::min<size_t>((nn + 255) / 256, 64));
+  const int64_t nn = s.nn();
+  HIP_TRY(hipMemcpyAsync(s.work, H, size_t(P) * size_t(nn) * sizeof(T), hipMemcpyDeviceToDevice, h->stream));
+  const unsigned gx = unsigned(std::min<size_t>((size_t(nn) + 255) / 256, 64));
   hipLaunchKernelGGL(large_identity_kernel<T>, dim3(gx, unsigned(P)), dim3(256), 0, h->stream, Cm, n);
-  int rc;
-  if constexpr (sizeof(T) == 4) {
-    rc = api.spotrf(h->blas, kFillUpper, n, work, n, int64_t(nn), info, int(P));
-    if (rc == 0) rc = api.spotrs(h->blas, kFillUpper, n, n, work, n, int64_t(nn), Cm, n, int64_t(nn), int(P));
-  } else {
-    rc = api.dpotrf(h->blas, kFillUpper, n, work, n, int64_t(nn), info, int(P));
-    if (rc == 0) rc = api.dpotrs(h->blas, kFillUpper, n, n, work, n, int64_t(nn), Cm, n, int64_t(nn), int(P));
-  }
+  int rc = api.potrf<T>(h->blas, kFillUpper, n, s.work, n, nn, s.info, int(P));
+  if (rc == 0) rc = api.potrs<T>(h->blas, kFillUpper, n, n, s.work, n, nn, Cm, n, nn, int(P));
   if (rc != 0) return toa_fail(TOA_E_HIP, "rocSOLVER potrf/potrs returned status " + std::to_string(rc));
-  hipLaunchKernelGGL(large_inv_finish_kernel<T>, dim3(unsigned(P)), dim3(256), 0, h->stream, Cm, info, ok, n);
+  hipLaunchKernelGGL(large_inv_finish_kernel<T>, dim3(unsigned(P)), dim3(256), 0, h->stream, Cm, s.info, ok, n);
   HIP_TRY(hipGetLastError());
   return TOA_OK;
 }
@@ -1690,28 +1669,52 @@ __global__ void __launch_bounds__(kCholThreads) large_chol_solve_kernel(const La
   if (tid == 0) a.info[p] = 0;
 }
 template <typename T>
-inline size_t chol_solve_lds_bytes(int n) { return (size_t(32) * 36 + size_t(n) * 36 + size_t(n) + 64 + 32) * sizeof(T) + 64; }
+inline size_t chol_solve_lds_bytes(int n) { return toa::chol_solve_lds_bytes(sizeof(T), n); }
 
 template <typename T>
-inline size_t ldlt_image_bytes(int n) { return ((size_t(n) * (n | 1) + 16) * sizeof(T) + 15) & ~size_t(15); }
+inline size_t ldlt_image_bytes(int n) { return toa::ldlt_image_bytes(sizeof(T), n); }
 template <typename T>
-const void* ldlt_solve_fn(int n) {
+auto ldlt_solve_fn(int n) -> void (*)(const LargeArgs<T>) {
   switch ((n + 15) / 16) {
-    case 1: case 2: case 3: case 4: return (const void*)large_ldlt_solve_kernel<T, 4>;
-    case 5: return (const void*)large_ldlt_solve_kernel<T, 5>;
-    case 6: return (const void*)large_ldlt_solve_kernel<T, 6>;
-    case 7: return (const void*)large_ldlt_solve_kernel<T, 7>;
-    default: return (const void*)large_ldlt_solve_kernel<T, 8>;
+    case 1: case 2: case 3: case 4: return large_ldlt_solve_kernel<T, 4>;
+    case 5: return large_ldlt_solve_kernel<T, 5>;
+    case 6: return large_ldlt_solve_kernel<T, 6>;
+    case 7: return large_ldlt_solve_kernel<T, 7>;
+    default: return large_ldlt_solve_kernel<T, 8>;
   }
 }
 template <typename T>
 void launch_ldlt_solve(int n, unsigned P, size_t lds, hipStream_t st, const LargeArgs<T>& a) {
-  switch ((n + 15) / 16) {
-    case 1: case 2: case 3: case 4: hipLaunchKernelGGL((large_ldlt_solve_kernel<T, 4>), dim3(P), dim3(256), lds, st, a); break;
-    case 5: hipLaunchKernelGGL((large_ldlt_solve_kernel<T, 5>), dim3(P), dim3(256), lds, st, a); break;
-    case 6: hipLaunchKernelGGL((large_ldlt_solve_kernel<T, 6>), dim3(P), dim3(256), lds, st, a); break;
-    case 7: hipLaunchKernelGGL((large_ldlt_solve_kernel<T, 7>), dim3(P), dim3(256), lds, st, a); break;
-    default: hipLaunchKernelGGL((large_ldlt_solve_kernel<T, 8>), dim3(P), dim3(256), lds, st, a); break;
+  hipLaunchKernelGGL(ldlt_solve_fn<T>(n), dim3(P), dim3(256), lds, st, a);
+}
+// the blocked Cholesky, with or without its look-ahead (toa_tuning::large_chol_no_lookahead): both raised to `lds` once ...
+template <typename T>
+int ensure_chol_solve_lds(toa_handle h, size_t lds) {
+  if (int rc = ensure_lds_attr(h, (const void*)large_chol_solve_kernel<T>, lds)) return rc;
+  return ensure_lds_attr(h, (const void*)large_chol_solve_kernel<T, false>, lds);
+}
+// ... and launched, one workgroup per matrix
+template <typename T>
+void launch_chol_solve(toa_handle h, unsigned P, size_t lds, hipStream_t st, const LargeArgs<T>& a) {
+  if (h->tune.large_chol_no_lookahead) hipLaunchKernelGGL((large_chol_solve_kernel<T, false>), dim3(P), dim3(kCholThreads), lds, st, a);
+  else hipLaunchKernelGGL(large_chol_solve_kernel<T>, dim3(P), dim3(kCholThreads), lds, st, a);
+}
+// the vectorised rows kernel by its trips per lane (KV = 1 .. 8)
+template <typename T>
+void launch_rows_vec(int KV, dim3 grid, size_t lds, hipStream_t st, const LargeArgs<T>& a, int LPR) {
+  static constexpr void (*kern[8])(const LargeArgs<T>, const int) = {
+      large_rows_vec_kernel<T, 1>, large_rows_vec_kernel<T, 2>, large_rows_vec_kernel<T, 3>, large_rows_vec_kernel<T, 4>,
+      large_rows_vec_kernel<T, 5>, large_rows_vec_kernel<T, 6>, large_rows_vec_kernel<T, 7>, large_rows_vec_kernel<T, 8>};
+  hipLaunchKernelGGL(kern[KV >= 1 && KV <= 7 ? KV - 1 : 7], grid, dim3(256), lds, st, a, LPR);
+}
+// the hand-written Gram by its tiles per wave (fp32 only; tri: the operand-sharing deal of 224 < n <= 256, three tiles per wave)
+template <typename T>
+void launch_gram(const SyrkGeom& geo, bool tri, dim3 grid, dim3 block, size_t lds, hipStream_t st, const LargeArgs<T>& a) {
+  if constexpr (sizeof(T) == 4) {
+    static constexpr void (*kern[5])(const LargeArgs<T>, const SyrkGeom) = {
+        large_gram_kernel<T, 1>, large_gram_kernel<T, 2>, large_gram_kernel<T, 3, true>, large_gram_kernel<T, 3>, large_gram_kernel<T, 4>};
+    const int tpw = geo.tpw;
+    hipLaunchKernelGGL(kern[tpw == 1 ? 0 : tpw == 2 ? 1 : tpw == 3 ? (tri ? 2 : 3) : 4], grid, block, lds, st, a, geo);
   }
 }
 
@@ -1962,23 +1965,39 @@ __global__ void __launch_bounds__(256) large_step_log_kernel(const char* __restr
   if (ninl) ninl[p] = S.cost_ninl;
 }
 
-// mode 0: the whole solve.  1 / 2 / 3: toa_lm_begin / toa_lm_step / toa_lm_stop on `state` (LargeStateLayout).
+// The five calls that share the pipeline (toa_large_lm_step's C-level `int mode` carries the same values).
+enum class LargeMode { Solve = 0, Begin = 1, Step = 2, Stop = 3, Accumulate = 4 };   // the whole solve; toa_lm_begin / _step / _stop; toa_accumulate's seam
+
+// Everything a call decides before its first stream operation: budgets, launch geometry, who does the Gram and the
+// factorisation.  Computed once by plan_large (no HIP call in it) and read by every piece below.
 template <typename T>
-int large_lm_run_t(toa_handle h, int n, int m, int64_t P, const T* data, T* x, const toa_options& opt,
-                   const toa_results& res, uint64_t* counters, int mode = 0, void* state = nullptr,
-                   int32_t* active_dev = nullptr, const int32_t* stop_request = nullptr, const LargeSeamOut<T>* seam_out = nullptr) {
-  const size_t nn = size_t(n) * n;
+struct LargePlan {
+  LargeMode mode;
+  bool seam, stepping;
+  int n, m;
+  long long P;
+  size_t nn;
+  unsigned max_tries;
+  long long max_passes, step_passes, pass_limit;   // the budget of a solve, of one stepped iteration, of this call
+  bool vec_ok; int KV, LPR, RPW; unsigned row_blocks; int gslots;   // rows kernel
+  bool own_gram, gram_tri; int gram_R, gram_rows; SyrkGeom geo;     // Gram
+  bool lu; LargeRouteChoice solver;                                 // factorisation
+  bool needs_lib, ahead, memo_on, robust;
+  int stage_rows, sum_stride;
+  size_t sum_bytes;
+};
+
+template <typename T>
+LargePlan<T> plan_large(toa_handle h, int n, int m, long long P, const toa_options& opt, LargeMode mode, const T* data) {
   auto al = [](size_t b) { return (b + 255) & ~size_t(255); };
-  const unsigned max_tries = opt.max_consec_failures > 0 ? (opt.max_consec_failures > 1 ? opt.max_consec_failures : 1) : 255;
-  const long long max_passes = (long long)(opt.max_iters + 2 + (opt.check_final_cost ? 1 : 0)) * (long long)(max_tries + 1);
-  const size_t b_st = al(size_t(P) * sizeof(LmState<T>)), b_i = al(size_t(P) * sizeof(int));
-  const size_t b_vec = al(size_t(P) * n * sizeof(T)), b_mat = al(size_t(P) * nn * sizeof(T));
-  const size_t b_J = al(size_t(P) * m * n * sizeof(T)), b_r = al(size_t(P) * m * sizeof(T));
-  const bool seam = mode == 4;              // toa_accumulate: one data pass, no Build (seam_out says where the results go)
-  const bool stepping = mode != 0 && !seam;
-  const LargeStateLayout<T> lay(n, P);
-  const long long step_passes = (long long)max_tries + 2;   // one iteration: a pass + its retries (optimizer.h:370-390)
-  const size_t b_sum = stepping ? al(size_t(4) * sizeof(int) * size_t(step_passes + 1)) : al(size_t(2) * sizeof(int) * size_t(max_passes + 1) * toa_context::kLanes);
+  LargePlan<T> pl;
+  pl.mode = mode; pl.n = n; pl.m = m; pl.P = P; pl.nn = size_t(n) * n;
+  pl.max_tries = opt.max_consec_failures > 0 ? (opt.max_consec_failures > 1 ? opt.max_consec_failures : 1) : 255;
+  pl.max_passes = (long long)(opt.max_iters + 2 + (opt.check_final_cost ? 1 : 0)) * (long long)(pl.max_tries + 1);
+  pl.seam = mode == LargeMode::Accumulate;   // toa_accumulate: one data pass, no Build (seam_out says where the results go)
+  pl.stepping = mode != LargeMode::Solve && !pl.seam;
+  pl.step_passes = (long long)pl.max_tries + 2;   // one iteration: a pass + its retries (optimizer.h:370-390)
+  pl.sum_bytes = pl.stepping ? al(size_t(4) * sizeof(int) * size_t(pl.step_passes + 1)) : al(size_t(2) * sizeof(int) * size_t(pl.max_passes + 1) * toa_context::kLanes);
   // vectorised rows kernel (see large_rows_vec_kernel): geometry and the per-wave J^T r partials
   constexpr int VEC = 16 / int(sizeof(T));
   // (n > 1024, round 5: the general rows kernel + the library's GEMM / GEMV / factorisation — the vectorised rows kernel keeps at most
@@ -1991,138 +2010,50 @@ int large_lm_run_t(toa_handle h, int n, int m, int64_t P, const T* data, T* x, c
   //  lanes per row.  Narrow rows — n = 4 .. 16 in fp32, 2 .. 8 in fp64 — have fewer and take the general rows kernel)
   const int KV0 = vec_shape ? (nv + LPR - 1) / LPR : 0;
   const int Rtrips = KV0 >= 5 ? 1 : (KV0 >= 3 ? 2 : (KV0 == 2 ? 4 : 8));
-  const bool vec_ok = vec_shape && LPR >= Rtrips;
-  const int KV = vec_ok ? KV0 : 0;
-  const int RPW = 64 / LPR;
+  pl.vec_ok = vec_shape && LPR >= Rtrips;
+  pl.KV = pl.vec_ok ? KV0 : 0;
+  pl.LPR = LPR;
+  pl.RPW = 64 / LPR;
   // (capped at one workgroup per compute unit and problem: every workgroup leaves four partial J^T r vectors that
   //  large_pre_kernel sums one after the other — 16 000 of them for ONE problem of 65 536 rows took longer than the data pass)
   const long long wg_target = std::min<long long>((long long)h->num_cus * 16 / std::max<long long>(1, P) + 1, h->num_cus);
-  const unsigned row_blocks = unsigned(std::max<long long>(1, std::min<long long>((m + 4 * (vec_ok ? RPW : 4) - 1) / (4 * (vec_ok ? RPW : 4)), wg_target)));
-  const int gslots = vec_ok ? int(row_blocks) * 4 : 0;
-  const size_t b_gpart = al(size_t(P) * size_t(std::max(gslots, 1)) * n * sizeof(T));
-  const size_t b_ptr = al(size_t(P) * sizeof(void*));
+  pl.row_blocks = unsigned(std::max<long long>(1, std::min<long long>((m + 4 * (pl.vec_ok ? pl.RPW : 4) - 1) / (4 * (pl.vec_ok ? pl.RPW : 4)), wg_target)));
+  pl.gslots = pl.vec_ok ? int(pl.row_blocks) * 4 : 0;
   // H = J^T J: the hand-written LDS-staged Gram (large_gram_kernel) for fp32 rows that are 16-byte aligned; the library GEMM
   // otherwise (fp64, odd shapes) or with toa_tuning::large_library_gram.  Same box, 128 problems x n = 256 x m = 8192 fp32
   // (profiles/r03_ab_log.md): rocblas_sgemm_batched 1.22 ms per pass with every problem rebuilding (the full square,
   // 113 TFLOP/s) plus the J = diag(s) A round trip through HBM in the rows kernel (0.43 -> 0.23 ms without it); this kernel
   // 0.74 ms (the lower tile triangle only: 56 % of the flops, at 104 TFLOP/s issued).
   const bool force_gemm = h->tune.large_library_gram != 0;
-  const bool own_gram = sizeof(T) == 4 && vec_ok && !force_gemm && n % 4 == 0;
-  int gram_R = 1, gram_rows = (m + 3) & ~3;
-  const SyrkGeom geo = syrk_geom(n);
+  pl.own_gram = sizeof(T) == 4 && pl.vec_ok && !force_gemm && n % 4 == 0;
+  pl.gram_R = 1; pl.gram_rows = (m + 3) & ~3;
+  pl.geo = syrk_geom(n);
+  const SyrkGeom& geo = pl.geo;
   // 224 < n <= 256: the operand-sharing deal of the tiles (syrk_stage_tri; toa_tuning::large_gram_plain_deal: the round-robin deal, same bits)
-  const bool gram_tri = !h->tune.large_gram_plain_deal && geo.nt == 8 && geo.groups == 1 && geo.waves == 12 && geo.tpw == 3;
-  if (own_gram) {   // about four workgroups per CU when every problem rebuilds (a late pass with few of them left is bound by ONE
-                    // workgroup's run time, which shrinks with the chunk); the rows of a chunk a multiple of the LDS stage
+  pl.gram_tri = !h->tune.large_gram_plain_deal && geo.nt == 8 && geo.groups == 1 && geo.waves == 12 && geo.tpw == 3;
+  if (pl.own_gram) {   // about four workgroups per CU when every problem rebuilds (a late pass with few of them left is bound by ONE
+                       // workgroup's run time, which shrinks with the chunk); the rows of a chunk a multiple of the LDS stage
     const long long want_wgs = (long long)h->num_cus * 4, per_chunk = P * geo.groups;
-    gram_R = int(std::max<long long>(1, std::min<long long>(256, (want_wgs + per_chunk - 1) / per_chunk)));   // (a FEW huge problems: up to 256 row chunks each)
-    gram_rows = (((m + gram_R - 1) / gram_R) + geo.K - 1) / geo.K * geo.K;
-    gram_R = (m + gram_rows - 1) / gram_rows;
+    pl.gram_R = int(std::max<long long>(1, std::min<long long>(256, (want_wgs + per_chunk - 1) / per_chunk)));   // (a FEW huge problems: up to 256 row chunks each)
+    pl.gram_rows = (((m + pl.gram_R - 1) / pl.gram_R) + geo.K - 1) / geo.K * geo.K;
+    pl.gram_R = (m + pl.gram_rows - 1) / pl.gram_rows;
   }
-  const size_t b_sc = own_gram ? al(size_t(P) * m * sizeof(T)) : 0;
-  const size_t b_gp = own_gram ? al(size_t(P) * gram_R * geo.T * 1024 * sizeof(T)) : 0;
-  const size_t b_Juse = own_gram ? 0 : b_J;   // J = diag(s) A is only materialised for the library GEMM
   // use_ldlt = false (gn.h:157-162): dx = -H.inverse() * g "without any checks on invertibility" (options.h:59) — a general LU
   // with partial pivoting from the library (what Eigen's inverse() is), its verdict ignored; the step is still refused if it is
   // not finite, as everywhere else in this path
-  const bool lu = !opt.use_ldlt;
-  const size_t b_piv = lu ? al(size_t(P) * n * sizeof(int)) : 0;
-  // what outlives a pass (LargeStateLayout) sits in the caller's state block in the stepping form, in the scratch otherwise
+  pl.lu = !opt.use_ldlt;
   // memo of linearisations (LargeArgs::skip ...): the whole-solve form only — the stepping form's state block has one H slot
-  const bool memo_on = !stepping && !seam && !h->tune.memo_off;
-  const size_t b_dbl = al(size_t(P) * sizeof(double));
-  const size_t b_memo = memo_on ? 5 * b_i + 4 * b_vec + 2 * b_dbl + 2 * b_mat : 0;
-  const bool robust = h->loss != TOA_LOSS_L2;
-  const size_t b_loss = robust ? b_r + b_i : 0;
-  const size_t need = (stepping ? 0 : lay.total) + 2 * b_i + 2 * b_vec + 2 * b_mat + b_Juse + b_r + b_sum + b_gpart + 2 * b_ptr + b_sc + b_gp + b_piv + b_memo + b_loss;
-  if (int rc = ensure_scratch(h, need, "large-n LM (the J scratch is P*m*n)")) return rc;
-  char* q = static_cast<char*>(h->scratch);
-  auto take = [&](size_t b) { char* r = q; q += b; return r; };
-  char* keep = stepping ? static_cast<char*>(state) : take(lay.total);
-  LargeArgs<T> a;
-  a.data = data; a.x = x; a.n = n; a.m = m; a.P = P; a.opt = opt; a.res = res;
-  a.counters = reinterpret_cast<unsigned long long*>(counters);
-  a.st = reinterpret_cast<LmState<T>*>(keep + lay.st);
-  a.active = reinterpret_cast<int*>(keep + lay.active);
-  a.built = reinterpret_cast<int*>(keep + lay.built);
-  a.g = reinterpret_cast<T*>(keep + lay.g); a.hd = reinterpret_cast<T*>(keep + lay.hd); a.dx = reinterpret_cast<T*>(keep + lay.dx);
-  a.ldx = reinterpret_cast<T*>(keep + lay.ldx); a.H = reinterpret_cast<T*>(keep + lay.H);
-  a.info = reinterpret_cast<int*>(take(b_i));
-  a.stepped = stepping ? reinterpret_cast<int*>(take(b_i)) : (take(b_i), nullptr);
-  a.active_out = active_dev; a.stop_request = stop_request;
-  a.gnew = reinterpret_cast<T*>(take(b_vec)); a.rhs = reinterpret_cast<T*>(take(b_vec));
-  a.Hnew = reinterpret_cast<T*>(take(b_mat)); a.work = reinterpret_cast<T*>(take(b_mat));
-  a.J = reinterpret_cast<T*>(take(b_Juse)); a.r = reinterpret_cast<T*>(take(b_r));
-  a.sc = reinterpret_cast<T*>(take(b_sc)); a.gram_part = reinterpret_cast<T*>(take(b_gp));
-  a.own_gram = own_gram ? 1 : 0; a.gram_R = gram_R; a.gram_rows = gram_rows;
-  a.summary = reinterpret_cast<int*>(take(b_sum));
-  a.gpart = reinterpret_cast<T*>(take(b_gpart));
-  a.gslots = gslots;
-  a.jptr = reinterpret_cast<const T**>(take(b_ptr));
-  a.hptr = reinterpret_cast<T**>(take(b_ptr));
-  int* ipiv = reinterpret_cast<int*>(take(b_piv));
-  a.skip = a.cur = a.midx = nullptr;
-  a.hslots = 1;
-  a.hdu = a.g_m = a.hdu_m = a.xs_m = nullptr;
-  a.lin_cost = a.memo_cost = nullptr;
-  a.lin_ninl = a.memo_ninl = nullptr;
-  a.loss = h->loss; a.th2 = T(h->loss_th2); a.lossv = nullptr; a.ninl = nullptr;
-  if (robust) { a.lossv = reinterpret_cast<T*>(take(b_r)); a.ninl = reinterpret_cast<int*>(take(b_i)); }
-  if (memo_on) {
-    a.lin_ninl = reinterpret_cast<int*>(take(b_i)); a.memo_ninl = reinterpret_cast<int*>(take(b_i));
-    a.skip = reinterpret_cast<int*>(take(b_i)); a.cur = reinterpret_cast<int*>(take(b_i)); a.midx = reinterpret_cast<int*>(take(b_i));
-    a.hdu = reinterpret_cast<T*>(take(b_vec)); a.g_m = reinterpret_cast<T*>(take(b_vec));
-    a.hdu_m = reinterpret_cast<T*>(take(b_vec)); a.xs_m = reinterpret_cast<T*>(take(b_vec));
-    a.lin_cost = reinterpret_cast<double*>(take(b_dbl)); a.memo_cost = reinterpret_cast<double*>(take(b_dbl));
-    a.H = reinterpret_cast<T*>(take(2 * b_mat));   // two slots per problem (the state block's single one stays unused)
-    a.hslots = 2;
-  }
-  hipStream_t st = h->stream;
-  // 64 <= n <= 128: the workgroup LDL^T above; beyond (or with toa_tuning::large_library_solver) rocSOLVER
-  const bool force_lib = h->tune.large_library_solver != 0;
-  const size_t chol_lds = ldlt_image_bytes<T>(n);
-  const bool own_chol = !lu && !force_lib && n <= 128 && chol_lds + 4096 <= size_t(h->max_lds);  // measured crossover (tools/k3_crossover.py)
-  if (own_chol) {
-    if (int rc = ensure_lds_attr(h, ldlt_solve_fn<T>(n), chol_lds)) return rc;
-  }
-  // beyond 128 unknowns: the one-workgroup blocked Cholesky + substitutions (large_chol_solve_kernel) while its panel fits the
-  // LDS (fp32: n <= 1024, fp64: n <= 512); the library beyond, for use_ldlt = false, and with toa_tuning::large_library_solver
-  const size_t chol2_lds = chol_solve_lds_bytes<T>(n);
-  const bool own_chol2 = !own_chol && !lu && !force_lib && n > 128 && chol2_lds + 2048 <= size_t(h->max_lds);
-  if (own_chol2) {
-    if (int rc = ensure_lds_attr(h, (const void*)large_chol_solve_kernel<T>, chol2_lds)) return rc;
-    if (int rc = ensure_lds_attr(h, (const void*)large_chol_solve_kernel<T, false>, chol2_lds)) return rc;
-  }
+  pl.memo_on = !pl.stepping && !pl.seam && !h->tune.memo_off;
+  pl.robust = h->loss != TOA_LOSS_L2;
+  // 64 <= n <= 128: the workgroup LDL^T; beyond, the one-workgroup blocked Cholesky while its panel fits the LDS; rocSOLVER
+  // otherwise (large_route.hpp)
+  pl.solver = large_route(size_t(h->max_lds), h->tune.large_library_solver != 0, sizeof(T), n, P, opt.use_ldlt);
+  const bool own_solver = pl.solver.route != LargeRoute::Library;
   // rocBLAS / rocSOLVER are opened (dlopen, a handle: a cold load of their code objects, minutes in a bare process) only
   // when a stage of THIS solve is theirs — fp32 with aligned rows up to n = 1024 never touches them
-  const bool needs_lib = seam ? !own_gram : !(own_gram && (own_chol || own_chol2));
-  static RocApi no_api;
-  RocApi& api = needs_lib ? roc_api() : no_api;
-  if (needs_lib) {
-    if (!api.ok) return toa_fail(TOA_E_UNSUPPORTED, "large-n LM needs rocBLAS + rocSOLVER for this shape: " + api.err);
-    if (int rc = ensure_blas(h, api)) return rc;
-  }
-  if (mode == 3) {   // toa_lm_stop
-    hipLaunchKernelGGL(large_stop_kernel<T>, dim3(unsigned(P)), dim3(256), 0, st, a);
-    HIP_TRY(hipGetLastError());
-    return TOA_OK;
-  }
-  if (mode <= 1 || seam) {   // the whole solve, or toa_lm_begin: construct the state (no data pass)
-    HIP_TRY(hipMemsetAsync(a.ldx, 0, b_vec, st));
-    HIP_TRY(hipMemsetAsync(a.dx, 0, b_vec, st));
-    HIP_TRY(hipMemsetAsync(a.g, 0, b_vec, st));
-    // counters ACCUMULATE on every path (fused, row-split, stepping, here): the caller zeroes them (include/tinyopt_amd.h)
-    hipLaunchKernelGGL(large_init_kernel<T>, dim3(unsigned((P + 255) / 256)), dim3(256), 0, st, a);
-    HIP_TRY(hipGetLastError());
-    if (mode == 1) return TOA_OK;
-    if (seam) hipLaunchKernelGGL(large_seam_prep_kernel<T>, dim3(unsigned((P + 255) / 256)), dim3(256), 0, st, a, seam_out->want_grad);
-  }
-  HIP_TRY(hipMemsetAsync(a.summary, 0, b_sum, st));
-  if (stepping) HIP_TRY(hipMemsetAsync(a.stepped, 0, b_i, st));
-  if (robust) HIP_TRY(hipMemsetAsync(a.ninl, 0, b_i, st));   // (the scratch block is shared between calls: the stepping form starts every step from zero)
-  const T one = 1, zero = 0;
+  pl.needs_lib = pl.seam ? !pl.own_gram : !(pl.own_gram && own_solver);
   // row slices of the n x n staging copies: ~8 workgroups per CU over the batch, at least 8 rows each
-  const int stage_rows = int(std::max<long long>(8, (long long)n * P / std::max<long long>(1, (long long)h->num_cus * 8)));
+  pl.stage_rows = int(std::max<long long>(8, (long long)n * P / std::max<long long>(1, (long long)h->num_cus * 8)));
   // Round 4: where every stage of a pass is a kernel of ours (hand-written Gram + own Cholesky: fp32, aligned rows, n <= 1024)
   // nothing in a pass needs a host-side count, every kernel skips the problems that have finished, and each pass leaves its
   // (active, want-Jacobian) pair in its own slot of `summary` — so the host enqueues kAhead passes ahead and looks at pass
@@ -2131,49 +2062,119 @@ int large_lm_run_t(toa_handle h, int n, int m, int64_t P, const T* data, T* x, c
   // The at most kAhead surplus passes after the last problem has finished are launches of kernels that return at once.
   // With a LIBRARY stage in the pass (rocBLAS GEMM sized by want_j, rocSOLVER over all P matrices) the pass-by-pass
   // hand-shake stays: a surplus library pass would cost more than the read-back.
-  constexpr int kAhead = 2, kRing = toa_context::kPassRing;
-  const bool ahead = !stepping && own_gram && (own_chol || own_chol2);
-  const int sum_stride = stepping ? 4 : 2;   // the stepping form also counts the retries still owed (slot 2)
-  const long long pass_limit = stepping ? step_passes : max_passes;
+  pl.ahead = !pl.stepping && pl.own_gram && own_solver;
+  pl.sum_stride = pl.stepping ? 4 : 2;   // the stepping form also counts the retries still owed (slot 2)
+  pl.pass_limit = pl.stepping ? pl.step_passes : pl.max_passes;
+  return pl;
+}
+
+// The per-problem device arrays of a call — ONE line each: v(pointer, elements per problem[, slots]).  The order of the lines
+// is the order of the blocks (each 256-byte aligned); carving them, the bytes they need and the shift of every pointer to a
+// lane's first problem all come from walking these two lists, so an array cannot be in one and missing from another.
+//   what outlives a pass: the blocks of LargeStateLayout, in its order — the caller's state block in the stepping form
+template <typename T, typename V>
+void large_state_arrays(LargeArgs<T>& a, const LargePlan<T>& pl, V& v) {
+  const size_t n = size_t(pl.n);
+  T* unused = nullptr;
+  v(a.st, 1); v(a.active, 1); v(a.built, 1);
+  v(a.g, n); v(a.hd, n); v(a.dx, n); v(a.ldx, n);
+  v(pl.memo_on ? unused : a.H, pl.nn);   // (under the memo H has two slots per problem, below: this single one stays unused)
+}
+//   what a pass works with: the context's scratch (ipiv is the one array that is not a member of LargeArgs: the library's pivots)
+template <typename T, typename V>
+void large_scratch_arrays(LargeArgs<T>& a, int*& ipiv, const LargePlan<T>& pl, V& v) {
+  const size_t n = size_t(pl.n), m = size_t(pl.m), nn = pl.nn;
+  v(a.info, 1);
+  v(a.stepped, 1);   // (the slot is there in every form, the pointer only in the stepping form: large_lm_run_t clears it otherwise)
+  v(a.gnew, n); v(a.rhs, n);
+  v(a.Hnew, nn); v(a.work, nn);
+  v(a.J, pl.own_gram ? 0 : m * n);   // J = diag(s) A is only materialised for the library GEMM
+  v(a.r, m);
+  v(a.sc, pl.own_gram ? m : 0);
+  v(a.gram_part, pl.own_gram ? size_t(pl.gram_R) * pl.geo.T * 1024 : 0);
+  v.fixed(a.summary, pl.sum_bytes);   // not per problem: two (four: stepping) counts per pass, a run of them per lane
+  v(a.gpart, size_t(std::max(pl.gslots, 1)) * n);   // (no lanes without the vectorised rows kernel: the one slot of gslots = 0 is never shifted)
+  v(a.jptr, 1); v(a.hptr, 1);
+  v(ipiv, pl.lu ? n : 0);
+  if (pl.robust) { v(a.lossv, m); v(a.ninl, 1); }
+  if (pl.memo_on) {
+    v(a.lin_ninl, 1); v(a.memo_ninl, 1);
+    v(a.skip, 1); v(a.cur, 1); v(a.midx, 1);
+    v(a.hdu, n); v(a.g_m, n); v(a.hdu_m, n); v(a.xs_m, n);
+    v(a.lin_cost, 1); v(a.memo_cost, 1);
+    v(a.H, nn, 2);   // two slots per problem (the state block's single one stays unused)
+  }
+}
+struct LargeCarve {   // gives every array its block behind `base` (NULL: only counts the bytes)
+  long long P;
+  char* base;
+  size_t off = 0;
+  template <typename U> void fixed(U*& p, size_t bytes) {
+    p = base ? reinterpret_cast<U*>(base + off) : nullptr;
+    off += (bytes + 255) & ~size_t(255);
+  }
+  template <typename U> void operator()(U*& p, size_t per, size_t slots = 1) { fixed(p, size_t(P) * per * sizeof(U)); off += (slots - 1) * ((size_t(P) * per * sizeof(U) + 255) & ~size_t(255)); }
+};
+struct LargeShift {   // moves every array that is there on to problem p0
+  long long p0;
+  template <typename U> void fixed(U*&, size_t) {}
+  template <typename U> void operator()(U*& p, size_t per, size_t slots = 1) { if (p) p += size_t(p0) * per * slots; }
+};
+// Carve the arrays of `a` (state == NULL: what outlives a pass goes to the front of the scratch too); returns the scratch bytes used.
+template <typename T>
+size_t carve_large(LargeArgs<T>& a, int*& ipiv, const LargePlan<T>& pl, char* state, char* scratch) {
+  LargeCarve keep{pl.P, pl.stepping ? state : scratch};
+  large_state_arrays(a, pl, keep);
+  LargeCarve rest{pl.P, scratch, pl.stepping ? 0 : keep.off};
+  large_scratch_arrays(a, ipiv, pl, rest);
+  return rest.off;
+}
+// `a` as a lane sees it: the problems [p0, p0 + Pl) of the batch
+template <typename T>
+void shift_large(LargeArgs<T>& a, const LargePlan<T>& pl, long long p0, long long Pl) {
+  LargeShift s{p0};
+  int* no_pivots = nullptr;   // (lanes run our own factorisation)
+  large_state_arrays(a, pl, s);
+  large_scratch_arrays(a, no_pivots, pl, s);
+  a.P = Pl;
+  a.data += size_t(p0) * pl.m * (size_t(pl.n) + 1);
+  a.x += p0 * pl.n;
+  a.res = results_at(a.res, p0, pl.n);
+}
+
+// One call of the pipeline: the plan, the arguments of its kernels, and the pieces large_lm_run_t dispatches over.
+template <typename T>
+struct LargeRun {
+  toa_handle h;
+  const LargePlan<T>& pl;
+  RocApi& api;
+  LargeArgs<T> a;
+  int* ipiv = nullptr;
+  const LargeSeamOut<T>* seam_out = nullptr;
+  static constexpr int kAhead = 2, kRing = toa_context::kPassRing;
 
   // One pass of the loop body for the problems of `la` (the whole batch, or one lane's share of it) on stream ls
-  auto enqueue_pass = [&](const LargeArgs<T>& la, hipStream_t ls, const long long Pl, int* sum_dev, int& want_j,
-                          hipEvent_t wait_first = nullptr, hipEvent_t record_after_gram = nullptr) -> int {
+  int enqueue_pass(const LargeArgs<T>& la, hipStream_t ls, const long long Pl, int* sum_dev, int& want_j,
+                   hipEvent_t wait_first = nullptr, hipEvent_t record_after_gram = nullptr) const {
+    const int n = pl.n, m = pl.m;
+    const int64_t nn = int64_t(pl.nn);
+    const T one = 1, zero = 0;
     if (wait_first) HIP_TRY(hipStreamWaitEvent(ls, wait_first, 0));
-    const dim3 rgrid(row_blocks, unsigned(Pl));
+    const dim3 rgrid(pl.row_blocks, unsigned(Pl));
     const size_t xs_bytes = size_t(n) * sizeof(T);
-    if (!vec_ok) {
-      hipLaunchKernelGGL(large_rows_kernel<T>, rgrid, dim3(256), xs_bytes, ls, la);
-    } else {
-      switch (KV) {
-        case 1: hipLaunchKernelGGL((large_rows_vec_kernel<T, 1>), rgrid, dim3(256), xs_bytes, ls, la, LPR); break;
-        case 2: hipLaunchKernelGGL((large_rows_vec_kernel<T, 2>), rgrid, dim3(256), xs_bytes, ls, la, LPR); break;
-        case 3: hipLaunchKernelGGL((large_rows_vec_kernel<T, 3>), rgrid, dim3(256), xs_bytes, ls, la, LPR); break;
-        case 4: hipLaunchKernelGGL((large_rows_vec_kernel<T, 4>), rgrid, dim3(256), xs_bytes, ls, la, LPR); break;
-        case 5: hipLaunchKernelGGL((large_rows_vec_kernel<T, 5>), rgrid, dim3(256), xs_bytes, ls, la, LPR); break;
-        case 6: hipLaunchKernelGGL((large_rows_vec_kernel<T, 6>), rgrid, dim3(256), xs_bytes, ls, la, LPR); break;
-        case 7: hipLaunchKernelGGL((large_rows_vec_kernel<T, 7>), rgrid, dim3(256), xs_bytes, ls, la, LPR); break;
-        default: hipLaunchKernelGGL((large_rows_vec_kernel<T, 8>), rgrid, dim3(256), xs_bytes, ls, la, LPR); break;
-      }
-    }
-    if (own_gram) {
+    if (!pl.vec_ok) hipLaunchKernelGGL(large_rows_kernel<T>, rgrid, dim3(256), xs_bytes, ls, la);
+    else launch_rows_vec<T>(pl.KV, rgrid, xs_bytes, ls, la, pl.LPR);
+    if (pl.own_gram) {
       if constexpr (sizeof(T) == 4) {
-        const dim3 ggrid(unsigned(geo.groups * gram_R), unsigned(Pl)), gblock(unsigned(geo.waves * 64));
+        const SyrkGeom& geo = pl.geo;
+        const dim3 ggrid(unsigned(geo.groups * pl.gram_R), unsigned(Pl)), gblock(unsigned(geo.waves * 64));
         const size_t glds = size_t(2) * geo.K * geo.ns * sizeof(T) + 256;   // (+ the one-step over-read of the operand prefetch)
-        switch (geo.tpw) {
-          case 1: hipLaunchKernelGGL((large_gram_kernel<T, 1>), ggrid, gblock, glds, ls, la, geo); break;
-          case 2: hipLaunchKernelGGL((large_gram_kernel<T, 2>), ggrid, gblock, glds, ls, la, geo); break;
-          case 3:
-            if (gram_tri) hipLaunchKernelGGL((large_gram_kernel<T, 3, true>), ggrid, gblock, glds, ls, la, geo);
-            else hipLaunchKernelGGL((large_gram_kernel<T, 3>), ggrid, gblock, glds, ls, la, geo);
-            break;
-          default: hipLaunchKernelGGL((large_gram_kernel<T, 4>), ggrid, gblock, glds, ls, la, geo); break;
-        }
+        launch_gram<T>(geo, pl.gram_tri, ggrid, gblock, glds, ls, la);
         hipLaunchKernelGGL(large_gram_reduce_kernel<T>, dim3(unsigned(geo.T), unsigned(Pl)), dim3(256), 0, ls, la, geo);
         if (record_after_gram) HIP_TRY(hipEventRecord(record_after_gram, ls));
       }
     } else if (want_j > 0) {
-      if (stepping) {   // the host has no count from a previous pass here: the list's length comes back with it
+      if (pl.stepping) {   // the host has no count from a previous pass here: the list's length comes back with it
         int* cnt_dev = sum_dev + 3;
         hipLaunchKernelGGL(large_compact_kernel<T>, dim3(1), dim3(256), 0, ls, la, cnt_dev);
         HIP_TRY(hipMemcpyAsync(&want_j, cnt_dev, sizeof(int), hipMemcpyDeviceToHost, ls));
@@ -2182,88 +2183,78 @@ int large_lm_run_t(toa_handle h, int n, int m, int64_t P, const T* data, T* x, c
         hipLaunchKernelGGL(large_compact_kernel<T>, dim3(1), dim3(256), 0, ls, la);
       }
     }
-    if (!own_gram && want_j > 0) {
-      int rc;  // J row-major [m][n] == column-major n x m (ld n):  H = Jc Jc^T,  g = Jc r
-      if constexpr (sizeof(T) == 4) {
-        rc = api.sgemm_b(h->blas, kOpN, kOpT, n, n, m, &one, la.jptr, n, la.jptr, n, &zero, la.hptr, n, want_j);
-        if (rc == 0 && !vec_ok) rc = api.sgemv(h->blas, kOpN, n, m, &one, la.J, n, int64_t(m) * n, la.r, 1, m, &zero, la.gnew, 1, n, int(Pl));
-      } else {
-        rc = api.dgemm_b(h->blas, kOpN, kOpT, n, n, m, &one, la.jptr, n, la.jptr, n, &zero, la.hptr, n, want_j);
-        if (rc == 0 && !vec_ok) rc = api.dgemv(h->blas, kOpN, n, m, &one, la.J, n, int64_t(m) * n, la.r, 1, m, &zero, la.gnew, 1, n, int(Pl));
-      }
+    if (!pl.own_gram && want_j > 0) {
+      // J row-major [m][n] == column-major n x m (ld n):  H = Jc Jc^T,  g = Jc r
+      int rc = api.gemm_batched<T>(h->blas, kOpN, kOpT, n, n, m, &one, la.jptr, n, la.jptr, n, &zero, la.hptr, n, want_j);
+      if (rc == 0 && !pl.vec_ok) rc = api.gemv<T>(h->blas, kOpN, n, m, &one, la.J, n, int64_t(m) * n, la.r, 1, int64_t(m), &zero, la.gnew, 1, int64_t(n), int(Pl));
       if (rc != 0) return toa_fail(TOA_E_HIP, "rocBLAS gemm/gemv returned status " + std::to_string(rc));
     }
-    if (seam) {
+    if (pl.seam) {
       hipLaunchKernelGGL(large_seam_out_kernel<T>, dim3(unsigned(Pl)), dim3(256), 0, ls, la, *seam_out);
       HIP_TRY(hipGetLastError());
       return TOA_OK;
     }
     hipLaunchKernelGGL(large_pre_kernel<T>, dim3(unsigned(Pl)), dim3(256), 0, ls, la);
-    hipLaunchKernelGGL(large_stage_kernel<T>, dim3(unsigned((n + stage_rows - 1) / stage_rows), unsigned(Pl)), dim3(256), 0, ls, la, stage_rows);
+    hipLaunchKernelGGL(large_stage_kernel<T>, dim3(unsigned((n + pl.stage_rows - 1) / pl.stage_rows), unsigned(Pl)), dim3(256), 0, ls, la, pl.stage_rows);
     int rc = 0;
-    if (own_chol) {
-      launch_ldlt_solve<T>(n, unsigned(Pl), chol_lds, ls, la);
-    } else if (own_chol2) {
-      if (h->tune.large_chol_no_lookahead) hipLaunchKernelGGL((large_chol_solve_kernel<T, false>), dim3(unsigned(Pl)), dim3(kCholThreads), chol2_lds, ls, la);
-      else hipLaunchKernelGGL(large_chol_solve_kernel<T>, dim3(unsigned(Pl)), dim3(kCholThreads), chol2_lds, ls, la);
-    } else if (lu) {
-      if constexpr (sizeof(T) == 4) {
-        rc = api.sgetrf(h->blas, n, n, la.work, n, int64_t(nn), ipiv, int64_t(n), la.info, int(Pl));
-        if (rc == 0) rc = api.sgetrs(h->blas, kOpN, n, 1, la.work, n, int64_t(nn), ipiv, int64_t(n), la.rhs, n, int64_t(n), int(Pl));
-      } else {
-        rc = api.dgetrf(h->blas, n, n, la.work, n, int64_t(nn), ipiv, int64_t(n), la.info, int(Pl));
-        if (rc == 0) rc = api.dgetrs(h->blas, kOpN, n, 1, la.work, n, int64_t(nn), ipiv, int64_t(n), la.rhs, n, int64_t(n), int(Pl));
-      }
+    if (pl.solver.route == LargeRoute::WorkgroupLdlt) {
+      launch_ldlt_solve<T>(n, unsigned(Pl), pl.solver.lds, ls, la);
+    } else if (pl.solver.route == LargeRoute::BlockedCholesky) {
+      launch_chol_solve<T>(h, unsigned(Pl), pl.solver.lds, ls, la);
+    } else if (pl.lu) {
+      rc = api.getrf<T>(h->blas, n, n, la.work, n, nn, ipiv, int64_t(n), la.info, int(Pl));
+      if (rc == 0) rc = api.getrs<T>(h->blas, kOpN, n, 1, la.work, n, nn, ipiv, int64_t(n), la.rhs, n, int64_t(n), int(Pl));
       HIP_TRY(hipMemsetAsync(la.info, 0, size_t(Pl) * sizeof(int), ls));   // unchecked: a singular pivot is not a failure by itself
-    } else if constexpr (sizeof(T) == 4) {
-      rc = api.spotrf(h->blas, kFillUpper, n, la.work, n, int64_t(nn), la.info, int(Pl));
-      if (rc == 0) rc = api.spotrs(h->blas, kFillUpper, n, 1, la.work, n, int64_t(nn), la.rhs, n, int64_t(n), int(Pl));
     } else {
-      rc = api.dpotrf(h->blas, kFillUpper, n, la.work, n, int64_t(nn), la.info, int(Pl));
-      if (rc == 0) rc = api.dpotrs(h->blas, kFillUpper, n, 1, la.work, n, int64_t(nn), la.rhs, n, int64_t(n), int(Pl));
+      rc = api.potrf<T>(h->blas, kFillUpper, n, la.work, n, nn, la.info, int(Pl));
+      if (rc == 0) rc = api.potrs<T>(h->blas, kFillUpper, n, 1, la.work, n, nn, la.rhs, n, int64_t(n), int(Pl));
     }
     if (rc != 0) return toa_fail(TOA_E_HIP, "rocSOLVER potrf/potrs returned status " + std::to_string(rc));
     hipLaunchKernelGGL(large_post_kernel<T>, dim3(unsigned(Pl)), dim3(256), 0, ls, la, sum_dev);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipGetLastError());
     return TOA_OK;
-  };
-
-  if (seam) {
-    int want_j = seam_out->want_grad ? int(P) : 0;
-    return enqueue_pass(a, st, P, a.summary, want_j);
   }
+
+  // toa_accumulate: the data pass alone
+  int run_accumulate_seam() const {
+    int want_j = seam_out->want_grad ? int(pl.P) : 0;
+    return enqueue_pass(a, h->stream, pl.P, a.summary, want_j);
+  }
+
   // Under stream capture (hipGraph) the host can look at nothing: where every stage is ours the whole pass budget is recorded —
   // max_passes passes, each kernel of which returns at once for the problems that have finished — and the graph replays the
   // solve with no host in the loop (one lane: a captured fork / join would only add edges).  A typical solve needs a fifth of
   // the budget; the rest costs ~40 us of empty launches per pass.  With a library stage in the pass there is no such form.
-  {
-    if (stream_is_capturing(st)) {
-      if (!ahead)
-        return toa_fail(TOA_E_UNSUPPORTED, "large-n LM under stream capture: only the solves whose every stage is a kernel of this library "
-                                           "(fp32, 16-byte aligned rows, use_ldlt, n <= 1024, not the stepping form) can be captured");
-      // The budget is an internal bound, not something the caller chose: with max_consec_failures == 0 a Build may be retried
-      // 255 times per iteration, i.e. tens of thousands of passes of ~7 kernels each — a graph of 10^5 nodes whose every replay
-      // pays ~40 us per empty pass.  Such a budget is refused here with the numbers; the eager call has no such limit.
-      constexpr long long kMaxCapturedPasses = 1024;
-      if (max_passes > kMaxCapturedPasses)
-        return toa_fail(TOA_E_UNSUPPORTED, "large-n LM under stream capture: the pass budget of these options is " + std::to_string(max_passes) +
-                                           " passes (~" + std::to_string(max_passes * 7) + " graph nodes, ~" + std::to_string(max_passes * 40 / 1000) +
-                                           " ms of empty launches per replay); at most " + std::to_string(kMaxCapturedPasses) +
-                                           " are recorded — set max_consec_failures > 0 (the retry bound per iteration) or lower max_iters");
-      h->shadow_retired = true;   // (a graph of this handle now exists: its workspaces are never freed under it, toa_release_workspace)
-      for (long long pass = 0; pass < max_passes; ++pass) {
-        int want_all = int(P);
-        if (int rc = enqueue_pass(a, st, P, a.summary + 2 * pass, want_all)) return rc;
-      }
-      return TOA_OK;
+  int record_captured() const {
+    const long long max_passes = pl.max_passes;
+    if (!pl.ahead)
+      return toa_fail(TOA_E_UNSUPPORTED, "large-n LM under stream capture: only the solves whose every stage is a kernel of this library "
+                                         "(fp32, 16-byte aligned rows, use_ldlt, n <= 1024, not the stepping form) can be captured");
+    // The budget is an internal bound, not something the caller chose: with max_consec_failures == 0 a Build may be retried
+    // 255 times per iteration, i.e. tens of thousands of passes of ~7 kernels each — a graph of 10^5 nodes whose every replay
+    // pays ~40 us per empty pass.  Such a budget is refused here with the numbers; the eager call has no such limit.
+    constexpr long long kMaxCapturedPasses = 1024;
+    if (max_passes > kMaxCapturedPasses)
+      return toa_fail(TOA_E_UNSUPPORTED, "large-n LM under stream capture: the pass budget of these options is " + std::to_string(max_passes) +
+                                         " passes (~" + std::to_string(max_passes * 7) + " graph nodes, ~" + std::to_string(max_passes * 40 / 1000) +
+                                         " ms of empty launches per replay); at most " + std::to_string(kMaxCapturedPasses) +
+                                         " are recorded — set max_consec_failures > 0 (the retry bound per iteration) or lower max_iters");
+    h->shadow_retired = true;   // (a graph of this handle now exists: its workspaces are never freed under it, toa_release_workspace)
+    for (long long pass = 0; pass < max_passes; ++pass) {
+      int want_all = int(pl.P);
+      if (int rc = enqueue_pass(a, h->stream, pl.P, a.summary + 2 * pass, want_all)) return rc;
     }
+    return TOA_OK;
   }
-  if (!ahead) {   // a library stage in the pass, or the stepping form: pass by pass, the counts read back behind each
-    int active = int(P), want_j = int(P);
-    for (long long pass = 0; pass < pass_limit && active > 0; ++pass) {
-      int* sum_dev = a.summary + sum_stride * pass;
-      if (int rc = enqueue_pass(a, st, P, sum_dev, want_j)) return rc;
+
+  // a library stage in the pass, or the stepping form: pass by pass, the counts read back behind each
+  int run_pass_by_pass() const {
+    hipStream_t st = h->stream;
+    const bool stepping = pl.stepping;
+    int active = int(pl.P), want_j = int(pl.P);
+    for (long long pass = 0; pass < pl.pass_limit && active > 0; ++pass) {
+      int* sum_dev = a.summary + pl.sum_stride * pass;
+      if (int rc = enqueue_pass(a, st, pl.P, sum_dev, want_j)) return rc;
       int sum_host[3] = {0, 0, 0};
       HIP_TRY(hipMemcpyAsync(sum_host, sum_dev, size_t(stepping ? 3 : 2) * sizeof(int), hipMemcpyDeviceToHost, st));
       HIP_TRY(hipStreamSynchronize(st));
@@ -2272,7 +2263,7 @@ int large_lm_run_t(toa_handle h, int n, int m, int64_t P, const T* data, T* x, c
       if (stepping) {   // another pass only for the problems whose solve is being retried
         if (sum_host[2] == 0) return TOA_OK;
         active = sum_host[2];
-        want_j = int(P);
+        want_j = int(pl.P);
       }
     }
     if (stepping) return TOA_OK;   // (retries are bounded by max_tries inside the state machine)
@@ -2289,97 +2280,140 @@ int large_lm_run_t(toa_handle h, int n, int m, int64_t P, const T* data, T* x, c
   // 128 x n = 256 — because a Gram workgroup (12 waves x 114 VGPRs at n = 256) leaves 152 registers per SIMD and the 8-wave
   // factorisation needs 224: the factorisations run on compute units the Gram does not have, the overlap is a partition of the chip and the chip-time of
   // a pass is conserved (profiles/r04_ab_log.md section 3).
-  if (int rc = ensure_pass_ring(h)) return rc;
-  int nlanes = h->tune.large_one_lane ? 1 : (P >= 16 ? 2 : 1);   // (measured, 128 x n = 256: 1 lane 80.5 k, 2: 85.5 k, 3: 85 k, 4: 85 k it/s)
-  // ... with the operand-sharing Gram (one lane's Gram 451 -> 420 us) ONE lane is the faster schedule: 9.59 ms per 128-problem solve
-  // against 9.93 with two lanes (plain deal, same call: 9.92 / 9.79) — profiles/r04_ab_log.md section 8d
-  if (gram_tri && h->tune.large_one_lane == 0) nlanes = 1;
-  if (h->tune.large_one_lane > 1) nlanes = std::min<int>(h->tune.large_one_lane, toa_context::kLanes);   // (A/B: an explicit lane count)
-  nlanes = int(std::min<long long>(nlanes, std::max<long long>(1, P)));
-  struct Lane { LargeArgs<T> a; hipStream_t st; long long P, pass; int active; bool done; int* host; hipEvent_t* ev; int* sums; };
-  Lane lane[toa_context::kLanes];
-  for (int l = 0; l < nlanes; ++l) {
-    const long long p0 = P * l / nlanes, p1 = P * (l + 1) / nlanes;
-    Lane& L = lane[l];
-    L.a = a;
-    L.P = p1 - p0; L.pass = 0; L.active = int(L.P); L.done = false;
-    L.st = l == 0 ? st : h->lane_stream[l - 1];
-    L.host = h->pass_flags + l * 2 * kRing;
-    L.ev = h->pass_done + l * kRing;
-    L.sums = a.summary + size_t(l) * 2 * size_t(max_passes + 1);
-    LargeArgs<T>& b = L.a;
-    b.P = L.P;
-    b.data += size_t(p0) * m * (size_t(n) + 1); b.x += p0 * n;
-    b.st += p0; b.active += p0; b.built += p0; b.info += p0;
-    b.g += p0 * n; b.hd += p0 * n; b.dx += p0 * n; b.ldx += p0 * n; b.gnew += p0 * n; b.rhs += p0 * n;
-    b.H += size_t(p0) * nn * size_t(a.hslots > 1 ? 2 : 1); b.Hnew += size_t(p0) * nn; b.work += size_t(p0) * nn;
-    if (a.skip) {
-      b.skip += p0; b.cur += p0; b.midx += p0; b.lin_cost += p0; b.memo_cost += p0; b.lin_ninl += p0; b.memo_ninl += p0;
-      b.hdu += p0 * n; b.g_m += p0 * n; b.hdu_m += p0 * n; b.xs_m += p0 * n;
+  int run_lanes() const {
+    hipStream_t st = h->stream;
+    const long long P = pl.P, max_passes = pl.max_passes;
+    if (int rc = ensure_pass_ring(h)) return rc;
+    int nlanes = h->tune.large_one_lane ? 1 : (P >= 16 ? 2 : 1);   // (measured, 128 x n = 256: 1 lane 80.5 k, 2: 85.5 k, 3: 85 k, 4: 85 k it/s)
+    // ... with the operand-sharing Gram (one lane's Gram 451 -> 420 us) ONE lane is the faster schedule: 9.59 ms per 128-problem solve
+    // against 9.93 with two lanes (plain deal, same call: 9.92 / 9.79) — profiles/r04_ab_log.md section 8d
+    if (pl.gram_tri && h->tune.large_one_lane == 0) nlanes = 1;
+    if (h->tune.large_one_lane > 1) nlanes = std::min<int>(h->tune.large_one_lane, toa_context::kLanes);   // (A/B: an explicit lane count)
+    nlanes = int(std::min<long long>(nlanes, std::max<long long>(1, P)));
+    struct Lane { LargeArgs<T> a; hipStream_t st; long long P, pass; int active; bool done; int* host; hipEvent_t* ev; int* sums; };
+    Lane lane[toa_context::kLanes];
+    for (int l = 0; l < nlanes; ++l) {
+      const long long p0 = P * l / nlanes, p1 = P * (l + 1) / nlanes;
+      Lane& L = lane[l];
+      L.a = a;
+      shift_large(L.a, pl, p0, p1 - p0);
+      L.P = p1 - p0; L.pass = 0; L.active = int(L.P); L.done = false;
+      L.st = l == 0 ? st : h->lane_stream[l - 1];
+      L.host = h->pass_flags + l * 2 * kRing;
+      L.ev = h->pass_done + l * kRing;
+      L.sums = a.summary + size_t(l) * 2 * size_t(max_passes + 1);
     }
-    b.r += size_t(p0) * m; b.sc += size_t(p0) * m;
-    if (b.lossv) { b.lossv += size_t(p0) * m; b.ninl += p0; }
-    b.gram_part += size_t(p0) * gram_R * geo.T * 1024;
-    b.gpart += size_t(p0) * size_t(std::max(gslots, 0)) * n;
-    toa_results& r = b.res;
-    auto adv = [&](auto*& ptr, size_t per) { if (ptr) ptr += size_t(p0) * per; };
-    adv(r.stop_reason, 1); adv(r.num_iters, 1); adv(r.num_failures, 1); adv(r.num_consec_failures, 1);
-    adv(r.final_cost, 1); adv(r.final_num_residuals, 1); adv(r.final_rerr_dec, 1); adv(r.final_hessian, nn);
-    adv(r.errs, size_t(r.hist_stride)); adv(r.deltas2, size_t(r.hist_stride)); adv(r.successes, size_t(r.hist_stride));
-    adv(r.final_inlier_ratio, 1);
-  }
-  struct Join {   // whatever happens below, nothing of ours is still running on the lane stream when the call returns
-    toa_handle h; bool forked = false, joined = false;
-    ~Join() { if (forked && !joined) for (hipStream_t s : h->lane_stream) if (s) (void)hipStreamSynchronize(s); }
-  } join{h};
-  if (nlanes > 1) {
-    HIP_TRY(hipEventRecord(h->lane_fork, st));
-    for (int l = 1; l < nlanes; ++l) HIP_TRY(hipStreamWaitEvent(lane[l].st, h->lane_fork, 0));
-    join.forked = true;
-  }
-  bool all_done = false;
-  while (!all_done) {
-    all_done = true;
+    struct Join {   // whatever happens below, nothing of ours is still running on the lane stream when the call returns
+      toa_handle h; bool forked = false, joined = false;
+      ~Join() { if (forked && !joined) for (hipStream_t s : h->lane_stream) if (s) (void)hipStreamSynchronize(s); }
+    } join{h};
+    if (nlanes > 1) {
+      HIP_TRY(hipEventRecord(h->lane_fork, st));
+      for (int l = 1; l < nlanes; ++l) HIP_TRY(hipStreamWaitEvent(lane[l].st, h->lane_fork, 0));
+      join.forked = true;
+    }
+    bool all_done = false;
+    while (!all_done) {
+      all_done = true;
+      for (int l = 0; l < nlanes; ++l) {
+        Lane& L = lane[l];
+        if (L.done) continue;
+        if (L.pass >= max_passes) { L.done = true; continue; }
+        if (L.pass >= kAhead) {
+          const int slot = int((L.pass - kAhead) % kRing);
+          HIP_TRY(hipEventSynchronize(L.ev[slot]));
+          L.active = L.host[2 * slot];
+          if (L.active == 0) { L.done = true; continue; }
+        }
+        int* sum_dev = L.sums + 2 * L.pass;
+        int want_all = int(L.P);
+        // the stagger: lane l's pass k starts when lane l - 1's Gram of pass k is done, so that from then on one lane's solve
+        // runs beside another's data pass instead of all the Grams (and then all the solves) sharing the chip in lockstep
+        hipEvent_t wait_ev = (l > 0 && !lane[l - 1].done) ? h->lane_gram[(l - 1) * kRing + L.pass % kRing] : nullptr;
+        hipEvent_t rec_ev = (l + 1 < nlanes) ? h->lane_gram[l * kRing + L.pass % kRing] : nullptr;
+        if (int rc = enqueue_pass(L.a, L.st, L.P, sum_dev, want_all, wait_ev, rec_ev)) return rc;
+        const int slot = int(L.pass % kRing);
+        HIP_TRY(hipMemcpyAsync(L.host + 2 * slot, sum_dev, 2 * sizeof(int), hipMemcpyDeviceToHost, L.st));
+        HIP_TRY(hipEventRecord(L.ev[slot], L.st));
+        ++L.pass;
+        all_done = false;
+      }
+    }
+    if (nlanes > 1) {
+      for (int l = 1; l < nlanes; ++l) {
+        HIP_TRY(hipEventRecord(h->lane_join[l - 1], lane[l].st));
+        HIP_TRY(hipStreamWaitEvent(st, h->lane_join[l - 1], 0));
+      }
+      join.joined = true;
+    }
     for (int l = 0; l < nlanes; ++l) {
       Lane& L = lane[l];
-      if (L.done) continue;
-      if (L.pass >= max_passes) { L.done = true; continue; }
-      if (L.pass >= kAhead) {
-        const int slot = int((L.pass - kAhead) % kRing);
-        HIP_TRY(hipEventSynchronize(L.ev[slot]));
-        L.active = L.host[2 * slot];
-        if (L.active == 0) { L.done = true; continue; }
+      if (L.active > 0 && L.pass > 0) {   // the pass budget ran out before a zero was seen: the LAST pass decides
+        HIP_TRY(hipStreamSynchronize(L.st));
+        L.active = L.host[2 * int((L.pass - 1) % kRing)];
       }
-      int* sum_dev = L.sums + 2 * L.pass;
-      int want_all = int(L.P);
-      // the stagger: lane l's pass k starts when lane l - 1's Gram of pass k is done, so that from then on one lane's solve
-      // runs beside another's data pass instead of all the Grams (and then all the solves) sharing the chip in lockstep
-      hipEvent_t wait_ev = (l > 0 && !lane[l - 1].done) ? h->lane_gram[(l - 1) * kRing + L.pass % kRing] : nullptr;
-      hipEvent_t rec_ev = (l + 1 < nlanes) ? h->lane_gram[l * kRing + L.pass % kRing] : nullptr;
-      if (int rc = enqueue_pass(L.a, L.st, L.P, sum_dev, want_all, wait_ev, rec_ev)) return rc;
-      const int slot = int(L.pass % kRing);
-      HIP_TRY(hipMemcpyAsync(L.host + 2 * slot, sum_dev, 2 * sizeof(int), hipMemcpyDeviceToHost, L.st));
-      HIP_TRY(hipEventRecord(L.ev[slot], L.st));
-      ++L.pass;
-      all_done = false;
+      if (L.active > 0) return toa_fail(TOA_E_HIP, "large-n LM: pass budget exhausted with active problems (internal error)");
     }
+    return TOA_OK;
   }
-  if (nlanes > 1) {
-    for (int l = 1; l < nlanes; ++l) {
-      HIP_TRY(hipEventRecord(h->lane_join[l - 1], lane[l].st));
-      HIP_TRY(hipStreamWaitEvent(st, h->lane_join[l - 1], 0));
-    }
-    join.joined = true;
+};
+
+// The n > 63 pipeline behind toa_large_lm_run, toa_large_lm_step (`state`: LargeStateLayout) and toa_large_accumulate_pipeline.
+template <typename T>
+int large_lm_run_t(toa_handle h, int n, int m, int64_t P, const T* data, T* x, const toa_options& opt,
+                   const toa_results& res, uint64_t* counters, LargeMode mode = LargeMode::Solve, void* state = nullptr,
+                   int32_t* active_dev = nullptr, const int32_t* stop_request = nullptr, const LargeSeamOut<T>* seam_out = nullptr) {
+  const LargePlan<T> pl = plan_large<T>(h, n, m, P, opt, mode, data);
+  auto al = [](size_t b) { return (b + 255) & ~size_t(255); };
+  const size_t b_i = al(size_t(P) * sizeof(int)), b_vec = al(size_t(P) * n * sizeof(T));
+  LargeArgs<T> a{};
+  int* ipiv = nullptr;
+  const size_t need = carve_large(a, ipiv, pl, nullptr, nullptr);
+  if (int rc = ensure_scratch(h, need, "large-n LM (the J scratch is P*m*n)")) return rc;
+  carve_large(a, ipiv, pl, static_cast<char*>(state), static_cast<char*>(h->scratch));
+  if (!pl.stepping) a.stepped = nullptr;
+  a.data = data; a.x = x; a.n = n; a.m = m; a.P = P; a.opt = opt; a.res = res;
+  a.counters = reinterpret_cast<unsigned long long*>(counters);
+  a.active_out = active_dev; a.stop_request = stop_request;
+  a.own_gram = pl.own_gram ? 1 : 0; a.gram_R = pl.gram_R; a.gram_rows = pl.gram_rows;
+  a.gslots = pl.gslots;
+  a.hslots = pl.memo_on ? 2 : 1;
+  a.loss = h->loss; a.th2 = T(h->loss_th2);
+  hipStream_t st = h->stream;
+  if (pl.solver.route == LargeRoute::WorkgroupLdlt) {
+    if (int rc = ensure_lds_attr(h, (const void*)ldlt_solve_fn<T>(n), pl.solver.lds)) return rc;
+  } else if (pl.solver.route == LargeRoute::BlockedCholesky) {
+    if (int rc = ensure_chol_solve_lds<T>(h, pl.solver.lds)) return rc;
   }
-  for (int l = 0; l < nlanes; ++l) {
-    Lane& L = lane[l];
-    if (L.active > 0 && L.pass > 0) {   // the pass budget ran out before a zero was seen: the LAST pass decides
-      HIP_TRY(hipStreamSynchronize(L.st));
-      L.active = L.host[2 * int((L.pass - 1) % kRing)];
-    }
-    if (L.active > 0) return toa_fail(TOA_E_HIP, "large-n LM: pass budget exhausted with active problems (internal error)");
+  static RocApi no_api;
+  RocApi& api = pl.needs_lib ? roc_api() : no_api;
+  if (pl.needs_lib) {
+    if (!api.ok) return toa_fail(TOA_E_UNSUPPORTED, "large-n LM needs rocBLAS + rocSOLVER for this shape: " + api.err);
+    if (int rc = ensure_blas(h, api)) return rc;
   }
-  return TOA_OK;
+  if (mode == LargeMode::Stop) {   // toa_lm_stop
+    hipLaunchKernelGGL(large_stop_kernel<T>, dim3(unsigned(P)), dim3(256), 0, st, a);
+    HIP_TRY(hipGetLastError());
+    return TOA_OK;
+  }
+  if (mode != LargeMode::Step) {   // the whole solve, toa_lm_begin or the seam: construct the state (no data pass)
+    HIP_TRY(hipMemsetAsync(a.ldx, 0, b_vec, st));
+    HIP_TRY(hipMemsetAsync(a.dx, 0, b_vec, st));
+    HIP_TRY(hipMemsetAsync(a.g, 0, b_vec, st));
+    // counters ACCUMULATE on every path (fused, row-split, stepping, here): the caller zeroes them (include/tinyopt_amd.h)
+    hipLaunchKernelGGL(large_init_kernel<T>, dim3(unsigned((P + 255) / 256)), dim3(256), 0, st, a);
+    HIP_TRY(hipGetLastError());
+    if (mode == LargeMode::Begin) return TOA_OK;
+    if (pl.seam) hipLaunchKernelGGL(large_seam_prep_kernel<T>, dim3(unsigned((P + 255) / 256)), dim3(256), 0, st, a, seam_out->want_grad);
+  }
+  HIP_TRY(hipMemsetAsync(a.summary, 0, pl.sum_bytes, st));
+  if (pl.stepping) HIP_TRY(hipMemsetAsync(a.stepped, 0, b_i, st));
+  if (pl.robust) HIP_TRY(hipMemsetAsync(a.ninl, 0, b_i, st));   // (the scratch block is shared between calls: the stepping form starts every step from zero)
+  const LargeRun<T> run{h, pl, api, a, ipiv, seam_out};
+  if (pl.seam) return run.run_accumulate_seam();
+  if (stream_is_capturing(st)) return run.record_captured();
+  if (!pl.ahead) return run.run_pass_by_pass();
+  return run.run_lanes();
 }
 
 
@@ -2392,34 +2426,42 @@ __global__ void __launch_bounds__(256) large_fill_ones_kernel(int* __restrict__ 
 }
 
 template <typename T>
-int large_solve_own_t(toa_handle h, int n, int64_t P, const T* H, const T* g, double scale, T* dx, int32_t* ok) {
-  const size_t nn = size_t(n) * n;
-  auto al = [](size_t b) { return (b + 255) & ~size_t(255); };
-  const size_t b_work = al(size_t(P) * nn * sizeof(T)), b_rhs = al(size_t(P) * n * sizeof(T)), b_i = al(size_t(P) * sizeof(int));
-  if (int rc = ensure_scratch(h, b_work + b_rhs + 2 * b_i, "large-n solve")) return rc;
-  char* base = static_cast<char*>(h->scratch);
+int large_solve_own_t(toa_handle h, const LargeRouteChoice& route, int n, int64_t P, const T* H, const T* g, double scale, T* dx, int32_t* ok) {
+  SolveScratch<T> s{h, n, P};
+  if (int rc = s.carve(1, 1)) return rc;
   LargeArgs<T> a;
   std::memset(&a, 0, sizeof(a));
   a.n = n;
   a.P = P;
-  a.work = reinterpret_cast<T*>(base);
-  a.rhs = reinterpret_cast<T*>(base + b_work);
-  a.info = reinterpret_cast<int*>(base + b_work + b_rhs);
-  a.active = reinterpret_cast<int*>(base + b_work + b_rhs + b_i);  // every matrix is solved, unless the caller masks some out
+  a.work = s.work;
+  a.rhs = s.rhs;
+  a.info = s.info;
+  a.active = s.extra;  // every matrix is solved, unless the caller masks some out
   a.built = a.active;
-  const size_t chol_lds = n <= 128 ? ldlt_image_bytes<T>(n) : chol_solve_lds_bytes<T>(n);
-  if (int rc = ensure_lds_attr(h, n <= 128 ? ldlt_solve_fn<T>(n) : (const void*)large_chol_solve_kernel<T>, chol_lds)) return rc;
-  if (n > 128) { if (int rc = ensure_lds_attr(h, (const void*)large_chol_solve_kernel<T, false>, chol_lds)) return rc; }
+  const bool ldlt = route.route == LargeRoute::WorkgroupLdlt;
+  if (int rc = ldlt ? ensure_lds_attr(h, (const void*)ldlt_solve_fn<T>(n), route.lds) : ensure_chol_solve_lds<T>(h, route.lds)) return rc;
   hipLaunchKernelGGL(large_fill_ones_kernel<T>, dim3(unsigned((P + 255) / 256)), dim3(256), 0, h->stream, a.active, (long long)P,
                      h->solve_mask, (long long)h->solve_mask_stride);
-  const unsigned gx = unsigned(std::min<size_t>((nn + 255) / 256, 64));
-  hipLaunchKernelGGL(large_damp_kernel<T>, dim3(gx, unsigned(P)), dim3(256), 0, h->stream, H, g, a.work, a.rhs, n, scale);
-  if (n <= 128) launch_ldlt_solve<T>(n, unsigned(P), chol_lds, h->stream, a);
-  else if (h->tune.large_chol_no_lookahead) hipLaunchKernelGGL((large_chol_solve_kernel<T, false>), dim3(unsigned(P)), dim3(kCholThreads), chol_lds, h->stream, a);
-  else hipLaunchKernelGGL(large_chol_solve_kernel<T>, dim3(unsigned(P)), dim3(kCholThreads), chol_lds, h->stream, a);
-  hipLaunchKernelGGL(large_finish_kernel<T>, dim3(unsigned(P)), dim3(256), 0, h->stream, a.rhs, a.info, dx, ok, n,
-                     (const int*)a.active);
-  HIP_TRY(hipGetLastError());
+  s.damp(H, g, scale);
+  if (ldlt) launch_ldlt_solve<T>(n, unsigned(P), route.lds, h->stream, a);
+  else launch_chol_solve<T>(h, unsigned(P), route.lds, h->stream, a);
+  return s.finish(dx, ok, a.active);
+}
+
+// the f32 / f64 fan-out of the C entry points: f(float()) or f(double())
+template <typename F>
+int by_dtype(int dtype, F&& f) { return dtype == TOA_F32 ? f(float()) : f(double()); }
+
+// The pipeline's kernels index problems through grid.y (65 535): a larger batch goes through it slice by slice — the
+// problems are independent, so the slices are just shorter batches (same bits), and the workspace is sized for one slice.
+// f(first problem, problems); run_empty: an empty batch still makes its one (empty) call.
+template <typename F>
+int by_slices(int64_t P, bool run_empty, F&& f) {
+  constexpr int64_t kSlice = 65535;
+  for (int64_t p0 = 0; p0 < P || (run_empty && p0 == 0); p0 += kSlice) {
+    if (int rc = f(p0, std::min<int64_t>(kSlice, P - p0))) return rc;
+    if (P <= 0) break;
+  }
   return TOA_OK;
 }
 
@@ -2431,9 +2473,9 @@ int toa_large_solve_each(toa_handle h, int dtype, int n, int64_t P, const void* 
 // caller that rebuilds H before every call anyway (bundle adjustment with lists: the reduced camera system of a pass).  Falls back to
 // toa_large_solve_each (one library call per matrix: batch-independent bits) where the one-workgroup Cholesky does not apply.  h->solve_mask as there.
 int toa_large_solve_inplace(toa_handle h, int dtype, int n, int64_t P, void* H, const void* g, void* dx, int32_t* ok) {
-  const size_t lds = (size_t(32) * 36 + size_t(n) * 37 + 96) * (dtype == TOA_F32 ? 4 : 8) + 64;   // chol_solve_lds_bytes
-  if (h->tune.large_library_solver != 0 || n <= 128 || P > 65535 || lds + 2048 > size_t(h->max_lds)) return toa_large_solve_each(h, dtype, n, P, H, g, 1.0, dx, ok);
-  auto run = [&](auto tag) -> int {
+  const toa::LargeRouteChoice route = toa::large_route(size_t(h->max_lds), h->tune.large_library_solver != 0, dtype == TOA_F32 ? 4 : 8, n, P, true);
+  if (route.route != toa::LargeRoute::BlockedCholesky) return toa_large_solve_each(h, dtype, n, P, H, g, 1.0, dx, ok);
+  return toa::by_dtype(dtype, [&](auto tag) -> int {
     using T = decltype(tag);
     toa::LargeArgs<T> a;
     std::memset(static_cast<void*>(&a), 0, sizeof(a));
@@ -2445,56 +2487,49 @@ int toa_large_solve_inplace(toa_handle h, int dtype, int n, int64_t P, void* H, 
     a.dok = ok;
     a.dmask = h->solve_mask;
     a.dmask_stride = (long long)h->solve_mask_stride;
-    const size_t chol_lds = toa::chol_solve_lds_bytes<T>(n);
-    if (int rc = toa::ensure_lds_attr(h, (const void*)toa::large_chol_solve_kernel<T>, chol_lds)) return rc;
-    if (int rc = toa::ensure_lds_attr(h, (const void*)toa::large_chol_solve_kernel<T, false>, chol_lds)) return rc;
-    if (h->tune.large_chol_no_lookahead) hipLaunchKernelGGL((toa::large_chol_solve_kernel<T, false>), dim3(unsigned(P)), dim3(toa::kCholThreads), chol_lds, h->stream, a);
-    else hipLaunchKernelGGL(toa::large_chol_solve_kernel<T>, dim3(unsigned(P)), dim3(toa::kCholThreads), chol_lds, h->stream, a);
+    if (int rc = toa::ensure_chol_solve_lds<T>(h, route.lds)) return rc;
+    toa::launch_chol_solve<T>(h, unsigned(P), route.lds, h->stream, a);
     HIP_TRY(hipGetLastError());
     return TOA_OK;
-  };
-  return dtype == TOA_F32 ? run(float()) : run(double());
+  });
 }
 
 int toa_large_solve(toa_handle h, int dtype, int n, int64_t P, const void* H, const void* g, double scale, void* dx,
                     int32_t* ok) {
-  const bool force_lib = h->tune.large_library_solver != 0;
-  const size_t chol_lds = ((size_t(n) * (n | 1) + 16) * (dtype == TOA_F32 ? 4 : 8) + 15) & ~size_t(15);
-  const size_t chol2_lds = (size_t(32) * 36 + size_t(n) * 37 + 96) * (dtype == TOA_F32 ? 4 : 8) + 64;   // chol_solve_lds_bytes
-  const bool own2 = n > 128 && P <= 65535 && chol2_lds + 2048 <= size_t(h->max_lds);   // the one-workgroup blocked Cholesky (fp32: n <= 1024, fp64: n <= 512)
-  if (!force_lib && ((n <= 128 && chol_lds + 4096 <= size_t(h->max_lds)) || own2)) {  // the workgroup LDL^T (ldlt_wg.hpp) / blocked Cholesky; the library beyond
-    if (dtype == TOA_F32)
-      return toa::large_solve_own_t<float>(h, n, P, static_cast<const float*>(H), static_cast<const float*>(g), scale, static_cast<float*>(dx), ok);
-    return toa::large_solve_own_t<double>(h, n, P, static_cast<const double*>(H), static_cast<const double*>(g), scale, static_cast<double*>(dx), ok);
-  }
+  // the workgroup LDL^T (ldlt_wg.hpp) / the one-workgroup blocked Cholesky (fp32: n <= 1024, fp64: n <= 512); the library beyond
+  const toa::LargeRouteChoice route = toa::large_route(size_t(h->max_lds), h->tune.large_library_solver != 0, dtype == TOA_F32 ? 4 : 8, n, P, true);
+  if (route.route != toa::LargeRoute::Library)
+    return toa::by_dtype(dtype, [&](auto tag) -> int {
+      using T = decltype(tag);
+      return toa::large_solve_own_t<T>(h, route, n, P, static_cast<const T*>(H), static_cast<const T*>(g), scale, static_cast<T*>(dx), ok);
+    });
   toa::RocApi& api = toa::roc_api();
   if (!api.ok) return toa_fail(TOA_E_UNSUPPORTED, "large-n solve needs rocSOLVER: " + api.err);
-  if (dtype == TOA_F32)
-    return toa::large_solve_t<float>(h, api, n, P, static_cast<const float*>(H), static_cast<const float*>(g), scale,
-                                     static_cast<float*>(dx), ok);
-  return toa::large_solve_t<double>(h, api, n, P, static_cast<const double*>(H), static_cast<const double*>(g), scale,
-                                    static_cast<double*>(dx), ok);
+  return toa::by_dtype(dtype, [&](auto tag) -> int {
+    using T = decltype(tag);
+    return toa::large_solve_t<T>(h, api, n, P, static_cast<const T*>(H), static_cast<const T*>(g), scale, static_cast<T*>(dx), ok);
+  });
 }
 
 int toa_large_solve_unchecked(toa_handle h, int dtype, int n, int64_t P, const void* H, const void* g, double scale, void* dx, int32_t* ok) {
   toa::RocApi& api = toa::roc_api();
   if (!api.ok) return toa_fail(TOA_E_UNSUPPORTED, "use_ldlt = false beyond one wavefront needs rocSOLVER (general LU): " + api.err);
-  if (dtype == TOA_F32)
-    return toa::large_solve_lu_t<float>(h, api, n, P, static_cast<const float*>(H), static_cast<const float*>(g), scale, static_cast<float*>(dx), ok);
-  return toa::large_solve_lu_t<double>(h, api, n, P, static_cast<const double*>(H), static_cast<const double*>(g), scale, static_cast<double*>(dx), ok);
+  return toa::by_dtype(dtype, [&](auto tag) -> int {
+    using T = decltype(tag);
+    return toa::large_solve_lu_t<T>(h, api, n, P, static_cast<const T*>(H), static_cast<const T*>(g), scale, static_cast<T*>(dx), ok);
+  });
 }
 
 int toa_large_solve_each(toa_handle h, int dtype, int n, int64_t P, const void* H, const void* g, double scale, void* dx, int32_t* ok) {
-  {  // our own kernels are batch-independent by construction (one workgroup per matrix, fixed-order sums): one launch for all
-    const bool force_lib = h->tune.large_library_solver != 0;
-    const size_t chol2_lds = (size_t(32) * 36 + size_t(n) * 37 + 96) * (dtype == TOA_F32 ? 4 : 8) + 64;
-    if (!force_lib && (n <= 128 || (P <= 65535 && chol2_lds + 2048 <= size_t(h->max_lds)))) return toa_large_solve(h, dtype, n, P, H, g, scale, dx, ok);
-  }
+  // our own kernels are batch-independent by construction (one workgroup per matrix, fixed-order sums): one launch for all
+  if (toa::large_route(size_t(h->max_lds), h->tune.large_library_solver != 0, dtype == TOA_F32 ? 4 : 8, n, P, true).route != toa::LargeRoute::Library)
+    return toa_large_solve(h, dtype, n, P, H, g, scale, dx, ok);
   toa::RocApi& api = toa::roc_api();
   if (!api.ok) return toa_fail(TOA_E_UNSUPPORTED, "large-n solve needs rocSOLVER: " + api.err);
-  if (dtype == TOA_F32)
-    return toa::large_solve_each_t<float>(h, api, n, P, static_cast<const float*>(H), static_cast<const float*>(g), scale, static_cast<float*>(dx), ok);
-  return toa::large_solve_each_t<double>(h, api, n, P, static_cast<const double*>(H), static_cast<const double*>(g), scale, static_cast<double*>(dx), ok);
+  return toa::by_dtype(dtype, [&](auto tag) -> int {
+    using T = decltype(tag);
+    return toa::large_solve_each_t<T>(h, api, n, P, static_cast<const T*>(H), static_cast<const T*>(g), scale, static_cast<T*>(dx), ok);
+  });
 }
 
 int toa_large_lm_run(toa_handle h, int dtype, int n, int m, int64_t P, const void* data, void* x, const toa_options* options,
@@ -2515,33 +2550,18 @@ int toa_large_lm_run(toa_handle h, int dtype, int n, int m, int64_t P, const voi
   const bool loss_needs_pipeline = h->loss != TOA_LOSS_L2 && dtype == TOA_F64 && n > 96;
   if (options->use_ldlt && !few_huge && !loss_needs_pipeline && toa_large_fused_eligible(h, dtype, n, m))
     return toa_large_fused_lm_run(h, dtype, n, m, P, data, x, options, results, counters);
-  // The pipeline's kernels index problems through grid.y (65 535): a larger batch goes through it slice by slice — the
-  // problems are independent, so the slices are just shorter batches (same bits), and the workspace is sized for one slice.
-  constexpr int64_t kSlice = 65535;
-  const size_t es = dtype == TOA_F32 ? 4 : 8;
-  for (int64_t p0 = 0; p0 < P || p0 == 0; p0 += kSlice) {
-    const int64_t Ps = std::min<int64_t>(kSlice, P - p0);
-    toa_results r = *results;
-    auto adv = [&](auto*& ptr, size_t per) { if (ptr) ptr += size_t(p0) * per; };
-    adv(r.stop_reason, 1); adv(r.num_iters, 1); adv(r.num_failures, 1); adv(r.num_consec_failures, 1);
-    adv(r.final_cost, 1); adv(r.final_num_residuals, 1); adv(r.final_rerr_dec, 1); adv(r.final_hessian, size_t(n) * n);
-    adv(r.errs, size_t(r.hist_stride)); adv(r.deltas2, size_t(r.hist_stride)); adv(r.successes, size_t(r.hist_stride));
-    adv(r.final_inlier_ratio, 1);
-    const char* d = static_cast<const char*>(data) + size_t(p0) * size_t(m) * (size_t(n) + 1) * es;
-    char* xs = static_cast<char*>(x) + size_t(p0) * size_t(n) * es;
-    int rc;
-    if (dtype == TOA_F32)
-      rc = toa::large_lm_run_t<float>(h, n, m, Ps, reinterpret_cast<const float*>(d), reinterpret_cast<float*>(xs), *options, r, counters);
-    else
-      rc = toa::large_lm_run_t<double>(h, n, m, Ps, reinterpret_cast<const double*>(d), reinterpret_cast<double*>(xs), *options, r, counters);
-    if (rc != TOA_OK) return rc;
-    if (P <= 0) break;
-  }
-  return TOA_OK;
+  return toa::by_slices(P, true, [&](int64_t p0, int64_t Ps) -> int {
+    const toa_results r = results_at(*results, p0, n);
+    return toa::by_dtype(dtype, [&](auto tag) -> int {
+      using T = decltype(tag);
+      return toa::large_lm_run_t<T>(h, n, m, Ps, static_cast<const T*>(data) + size_t(p0) * size_t(m) * (size_t(n) + 1),
+                                    static_cast<T*>(x) + size_t(p0) * size_t(n), *options, r, counters);
+    });
+  });
 }
 
-// The stepping form at n >= 64 (toa_lm_begin / toa_lm_step / toa_lm_stop, capi.hip): mode 1 / 2 / 3 on the launch-per-stage
-// pipeline — every n >= 64, either solver flavour — with what outlives a pass kept in the caller's state block.
+// The stepping form at n >= 64 (toa_lm_begin / toa_lm_step / toa_lm_stop, capi.hip): LargeMode Begin / Step / Stop (mode 1 / 2 / 3) on the
+// launch-per-stage pipeline — every n >= 64, either solver flavour — with what outlives a pass kept in the caller's state block.
 size_t toa_large_state_bytes(int dtype, int n, int64_t P) {
   return dtype == TOA_F32 ? toa::LargeStateLayout<float>(n, P).total : toa::LargeStateLayout<double>(n, P).total;
 }
@@ -2550,11 +2570,11 @@ int toa_large_lm_step(toa_handle h, int dtype, int n, int m, int64_t P, const vo
                       const toa_results* results, uint64_t* counters, int mode, void* state, int32_t* active_dev,
                       const int32_t* stop_request) {
   if (P > 65535) return toa_fail(TOA_E_UNSUPPORTED, "stepping form at n >= 64: at most 65 535 problems per call");
-  if (dtype == TOA_F32)
-    return toa::large_lm_run_t<float>(h, n, m, P, static_cast<const float*>(data), static_cast<float*>(x), *options, *results,
-                                      counters, mode, state, active_dev, stop_request);
-  return toa::large_lm_run_t<double>(h, n, m, P, static_cast<const double*>(data), static_cast<double*>(x), *options, *results,
-                                     counters, mode, state, active_dev, stop_request);
+  return toa::by_dtype(dtype, [&](auto tag) -> int {
+    using T = decltype(tag);
+    return toa::large_lm_run_t<T>(h, n, m, P, static_cast<const T*>(data), static_cast<T*>(x), *options, *results, counters,
+                                  static_cast<toa::LargeMode>(mode), state, active_dev, stop_request);
+  });
 }
 
 // toa_accumulate for the natural layout where the one-launch kernel of large_fused.hip does not reach: n > 128, or an M-estimator
@@ -2564,53 +2584,44 @@ int toa_large_accumulate_pipeline(toa_handle h, int dtype, int n, int m, int64_t
   toa_options opt;
   toa_options_default(&opt);
   toa_results res{};
-  constexpr int64_t kSlice = 65535;
-  const size_t es = dtype == TOA_F32 ? 4 : 8;
-  for (int64_t p0 = 0; p0 < P; p0 += kSlice) {
-    const int64_t Ps = std::min<int64_t>(kSlice, P - p0);
-    const char* d = static_cast<const char*>(data) + size_t(p0) * size_t(m) * (size_t(n) + 1) * es;
-    char* xs = const_cast<char*>(static_cast<const char*>(x)) + size_t(p0) * size_t(n) * es;
-    char* gs = g ? static_cast<char*>(g) + size_t(p0) * size_t(n) * es : nullptr;
-    char* Hs = H ? static_cast<char*>(H) + size_t(p0) * size_t(n) * size_t(n) * es : nullptr;
-    int32_t* nr = nres ? nres + p0 : nullptr;
-    int rc;
-    if (dtype == TOA_F32) {
-      const toa::LargeSeamOut<float> o{reinterpret_cast<float*>(gs), reinterpret_cast<float*>(Hs), cost + p0, nr, want_grad};
-      rc = toa::large_lm_run_t<float>(h, n, m, Ps, reinterpret_cast<const float*>(d), reinterpret_cast<float*>(xs), opt, res, nullptr, 4, nullptr, nullptr, nullptr, &o);
-    } else {
-      const toa::LargeSeamOut<double> o{reinterpret_cast<double*>(gs), reinterpret_cast<double*>(Hs), cost + p0, nr, want_grad};
-      rc = toa::large_lm_run_t<double>(h, n, m, Ps, reinterpret_cast<const double*>(d), reinterpret_cast<double*>(xs), opt, res, nullptr, 4, nullptr, nullptr, nullptr, &o);
-    }
-    if (rc != TOA_OK) return rc;
-  }
-  return TOA_OK;
+  return toa::by_slices(P, false, [&](int64_t p0, int64_t Ps) -> int {
+    return toa::by_dtype(dtype, [&](auto tag) -> int {
+      using T = decltype(tag);
+      const toa::LargeSeamOut<T> o{g ? static_cast<T*>(g) + size_t(p0) * size_t(n) : nullptr, H ? static_cast<T*>(H) + size_t(p0) * size_t(n) * size_t(n) : nullptr,
+                                   cost + p0, nres ? nres + p0 : nullptr, want_grad};
+      return toa::large_lm_run_t<T>(h, n, m, Ps, static_cast<const T*>(data) + size_t(p0) * size_t(m) * (size_t(n) + 1),
+                                    const_cast<T*>(static_cast<const T*>(x)) + size_t(p0) * size_t(n), opt, res, nullptr, toa::LargeMode::Accumulate,
+                                    nullptr, nullptr, nullptr, &o);
+    });
+  });
 }
 
 int toa_large_step_info(toa_handle h, int dtype, int n, int64_t P, const void* state, double* err, double* dx2, double* g2,
                         void* dx_out, void* g_out) {
-  if (dtype == TOA_F32)
-    hipLaunchKernelGGL(toa::large_step_info_kernel<float>, dim3(unsigned(P)), dim3(256), 0, h->stream, static_cast<const char*>(state),
-                       (long long)P, n, err, dx2, g2, static_cast<float*>(dx_out), static_cast<float*>(g_out));
-  else
-    hipLaunchKernelGGL(toa::large_step_info_kernel<double>, dim3(unsigned(P)), dim3(256), 0, h->stream, static_cast<const char*>(state),
-                       (long long)P, n, err, dx2, g2, static_cast<double*>(dx_out), static_cast<double*>(g_out));
-  HIP_TRY(hipGetLastError());
-  return TOA_OK;
+  return toa::by_dtype(dtype, [&](auto tag) -> int {
+    using T = decltype(tag);
+    hipLaunchKernelGGL(toa::large_step_info_kernel<T>, dim3(unsigned(P)), dim3(256), 0, h->stream, static_cast<const char*>(state),
+                       (long long)P, n, err, dx2, g2, static_cast<T*>(dx_out), static_cast<T*>(g_out));
+    HIP_TRY(hipGetLastError());
+    return TOA_OK;
+  });
 }
 
 int toa_large_step_log(toa_handle h, int dtype, int n, int64_t P, const void* state, double* lambda, int32_t* nres, int32_t* ninl) {
-  const unsigned grid = unsigned((P + 255) / 256);
-  if (dtype == TOA_F32)
-    hipLaunchKernelGGL(toa::large_step_log_kernel<float>, dim3(grid), dim3(256), 0, h->stream, static_cast<const char*>(state), (long long)P, n, lambda, nres, ninl);
-  else
-    hipLaunchKernelGGL(toa::large_step_log_kernel<double>, dim3(grid), dim3(256), 0, h->stream, static_cast<const char*>(state), (long long)P, n, lambda, nres, ninl);
-  HIP_TRY(hipGetLastError());
-  return TOA_OK;
+  return toa::by_dtype(dtype, [&](auto tag) -> int {
+    using T = decltype(tag);
+    hipLaunchKernelGGL(toa::large_step_log_kernel<T>, dim3(unsigned((P + 255) / 256)), dim3(256), 0, h->stream, static_cast<const char*>(state),
+                       (long long)P, n, lambda, nres, ninl);
+    HIP_TRY(hipGetLastError());
+    return TOA_OK;
+  });
 }
 
 int toa_large_inv_cov(toa_handle h, int dtype, int n, int64_t P, const void* H, void* C, int32_t* ok) {
   toa::RocApi& api = toa::roc_api();
   if (!api.ok) return toa_fail(TOA_E_UNSUPPORTED, "large-n covariance needs rocSOLVER: " + api.err);
-  if (dtype == TOA_F32) return toa::large_inv_t<float>(h, api, n, P, static_cast<const float*>(H), static_cast<float*>(C), ok);
-  return toa::large_inv_t<double>(h, api, n, P, static_cast<const double*>(H), static_cast<double*>(C), ok);
+  return toa::by_dtype(dtype, [&](auto tag) -> int {
+    using T = decltype(tag);
+    return toa::large_inv_t<T>(h, api, n, P, static_cast<const T*>(H), static_cast<T*>(C), ok);
+  });
 }

@@ -167,6 +167,8 @@ int toa_create(toa_handle* out, int device, void* stream);
  *      that still allocates 4 entries would be written out of bounds by the memo counter), toa_tuning / toa_jit_spec exist.
  *      The host mirrors (include/tinyopt_amd/tinyopt.hpp, tinyopt_amd/_capi.py) refuse a library whose version differs. */
 #define TOA_ABI_VERSION 7   /* 7: toa_gd_options, toa_jit_gd_run, TOA_JIT_COST / TOA_JIT_COST_GRAD */
+/* Added under version 7 (additive: new functions, and fields carved out of words every caller already zeroes):
+ *   toa_jit_spec::diff / diff_h (the first two words of what was reserved[6]), TOA_DIFF_*, toa_jit_check_gradient. */
 int toa_abi_version(void);
 
 /* ---- tuning (per handle).  The arms of the A/B logs (profiles/r0N_ab_log.md) and of the bit-identity tests, as typed state
@@ -521,13 +523,34 @@ int toa_model_compile(toa_handle h, int dtype, int num_params, int residuals_per
  * SolverGD::Build's accumulation: g = sum_i grad c_i, cost = sum_i c_i, nres = 1; H_dev must be NULL. */
 #define TOA_JIT_COST 2
 #define TOA_JIT_COST_GRAD 3
+/* Numerical differentiation (the reference's diff/num_diff.h: NumEval, EstimateNumJac, CreateNumDiffFunc1 / 2 with
+ * Method::{kForward, kCentral, kFastCentral}): spec.diff != 0 differentiates a TOA_JIT_RESIDUAL or TOA_JIT_COST body by finite
+ * differences with step spec.diff_h instead of Jets, so the body is only ever instantiated on plain T (S = T) and need not be
+ * generic over its scalar type (tests/diff.cpp:113-132).
+ *   forward       (r(x + h e_a) - r(x)) / h
+ *   central       (r(x + h e_a) - r(x - h e_a)) / (2 h), both points formed from x
+ *   fast central  (r(y) - r(y + (-2 h) e_a)) / (2 h), y = x + h e_a
+ * A numeric residual model is a row model (a row per lane on the matrix-core Gram) at every 1 <= num_params <= 63 and
+ * 1 <= residuals_per_item <= 8; toa_set_loss applies as to AD models.  A numeric cost model differences each ITEM's cost term
+ * (the reference differences the summed cost, which in fp32 over thousands of items has lost the digits the difference needs).
+ * Cost: 2 n + 1 (forward: n + 1) evaluations of the body per item and pass.
+ * Served by toa_jit_lm_run (never by its automatic row-split route), toa_jit_accumulate, toa_jit_gd_run, toa_jit_model_stats.
+ * Refused: TOA_JIT_ACCUMULATE / TOA_JIT_COST_GRAD (TOA_E_ARG: CreateNumDiffFunc* takes residuals, not derivatives), manifold !=
+ * TOA_MANIFOLD_EUCLID (TOA_E_UNSUPPORTED), a negative or non-finite diff_h (TOA_E_ARG); toa_jit_lm_run_split and
+ * toa_jit_lm_begin / step / stop on such a model (TOA_E_UNSUPPORTED). */
+#define TOA_DIFF_DEFAULT 0
+#define TOA_DIFF_NUM_FORWARD 1
+#define TOA_DIFF_NUM_CENTRAL 2
+#define TOA_DIFF_NUM_FAST_CENTRAL 3
 typedef struct toa_jit_spec {
   int32_t dtype, num_params, residuals_per_item, scalars_per_item, header_scalars;
   int32_t manifold;   /* TOA_MANIFOLD_* */
   int32_t kind;       /* TOA_JIT_* */
   int32_t x_scalars;  /* TOA_MANIFOLD_USER: scalars of x as STORED ([P][x_scalars]; 1 .. 32, beyond 12 parameters 1 .. 64); num_params = the tangent's dimension */
   const char* plus_body;   /* TOA_MANIFOLD_USER: the body of `template <class S> void plus(const T* x, const S* d, S* xp)`: xp = x (+) d */
-  int32_t reserved[6];
+  int32_t diff;       /* TOA_DIFF_*: how the body is differentiated (0 = as before: Jets, or the body's own derivatives) */
+  float diff_h;       /* TOA_DIFF_NUM_*: the step h; 0 = FloatEpsilon<T> (1e-4f / 1e-7f, math.h:298-301) */
+  int32_t reserved[4];   /* (diff and diff_h were reserved[0..1]: the size and every other offset are what they were) */
 } toa_jit_spec;
 int toa_model_compile_ex(toa_handle h, const toa_jit_spec* spec, const char* body, toa_jit_model* out, char* log_out, size_t log_cap);
 int toa_jit_set_cache_dir(const char* dir);
@@ -544,6 +567,22 @@ int toa_jit_lm_run(toa_handle h, toa_jit_model model, int num_items, int64_t P, 
                    const toa_options* options, const toa_results* results, uint64_t* counters_dev);
 int toa_jit_accumulate(toa_handle h, toa_jit_model model, int num_items, int64_t P, const void* data_dev, const void* x_dev,
                        int want_grad, void* g_dev, void* H_dev, double* cost_dev, int32_t* nres_dev);
+/*      CheckGradient / CheckResidualsGradient (diff/gradient_check.h) for a run-time model of ANY kind at x_dev [P][num_params]:
+ *      the model's Accumulate seam against that of its NUMERIC TWIN — the same body wrapped in finite differences
+ *      (method: TOA_DIFF_NUM_*, step h = eps / 10, gradient_check.h:96,201), built on first use, cached on disk and held by the
+ *      model until toa_model_destroy.  eps <= 0: the reference's default (1e-2 for fp32, 1e-5 for fp64).
+ *        residual kinds  g = J^T r and, with check_H, H = J^T J  (CheckResidualsGradient compares the gradients of 0.5 |r|^2 and
+ *                        J^T J: the 0.5 is on both sides)
+ *        cost kinds      g only (CheckGradient); the H distance is 0 and ignored, as with check_H = 0
+ *      max_dist_dev [P][2] (optional): max |g - g_num|, max |H - H_num|, in the model's precision; ok_dev [P] (optional): both < eps.
+ *      Euclidean models on a handle without a loss; stream-ordered.  Refused with TOA_E_UNSUPPORTED when the twin would have to
+ *      be built, or the handle's workspace to grow, under stream capture: run the call once before hipStreamBeginCapture.
+ *      A TOA_JIT_ACCUMULATE / TOA_JIT_COST_GRAD body is checkable when it reads the parameters ONLY as x[j]: the twin hands it x as
+ *      an accessor (x[j] plus the step at the perturbed column), not as a const T*.  A body that takes x as a pointer (const T* xx = x;
+ *      x + k; x passed to a helper) runs, but its twin does not build: TOA_E_ARG, toa_last_error() says so with the compiler's log.
+ *      Numeric bodies (toa_jit_spec::diff, and every twin) are compiled without floating-point contraction. */
+int toa_jit_check_gradient(toa_handle h, toa_jit_model model, int num_items, int64_t P, const void* data_dev, const void* x_dev,
+                           double eps, int method, int check_H, double* max_dist_dev, int32_t* ok_dev);
 /*      Gradient descent (ABI 7): Optimize(x, cost, options) with options.solver_type = GradientDescent on a scalar cost model —
  *      gd::Optimizer = Optimizer_<SolverGD> (optimizers/gd.h; optimizer.h:242-539): every Step builds g = sum_i grad c_i (clamped by
  *      grad_clipping), dx = -lr * g, and judges, rolls back and stops exactly as the LM path does; no final Hessian is written

@@ -338,6 +338,11 @@ struct SE3Reproj : PlainModel<Scalar, TOA_MODEL_SE3_REPROJ> {
 // body: generic in its scalar type S; x[j] parameter j, p[k] the item's scalars, h[k] the header scalars, r[q] the residuals:
 //   JitResidual<double> fit(ctx, "const S dx = p[0] - x[0]; const S dy = p[1] - x[1]; r[0] = dx*dx + dy*dy - x[2]*x[2];", 3, 2);
 //   auto out = Optimize(x, fit.bind(P, npts, obs));                                            // tests/circle.cpp:32-68
+// diff/num_diff.h:20-52: how a run-time body is differentiated numerically (JitResidual's `diff`, diff::CheckGradient's `method`)
+namespace diff {
+enum Method { kForward = 0, kCentral, kFastCentral };
+inline int to_pod(Method m) { return m == kForward ? TOA_DIFF_NUM_FORWARD : (m == kCentral ? TOA_DIFF_NUM_CENTRAL : TOA_DIFF_NUM_FAST_CENTRAL); }
+}  // namespace diff
 template <typename Scalar>
 class JitModel;
 template <typename Scalar>
@@ -352,15 +357,20 @@ class JitResidual {
   // manifold = TOA_MANIFOLD_USER (round 5): the caller's own parameter container — tinyopt's traits::params_trait<T> (traits.h:103-359) as text:
   //   x_scalars = the container as stored, n = the dimension of its tangent, plus_body = the body of
   //   `template <class S> void plus(const T* x, const S* d, S* xp)`, xp = x (+) d (PlusEq on plain T; differentiated through Jets seeded on d).
+  // diff: TOA_DIFF_DEFAULT (Jets, or the body's own derivatives), or TOA_DIFF_NUM_* (diff::to_pod(diff::kCentral) ...) — a TOA_JIT_RESIDUAL /
+  //   TOA_JIT_COST body differentiated by finite differences with step diff_h (0 = FloatEpsilon<Scalar>), CreateNumDiffFunc1 / 2 of
+  //   diff/num_diff.h: the body runs on plain Scalar only.  Euclidean; no stop callbacks / max_duration_ms / log line.
   JitResidual(const Context& ctx, const std::string& body, int n, int item_scalars, int residuals_per_item = 1, int header_scalars = 0,
-              int manifold = TOA_MANIFOLD_EUCLID, int kind = TOA_JIT_RESIDUAL, const std::string& plus_body = std::string(), int x_scalars = 0)
+              int manifold = TOA_MANIFOLD_EUCLID, int kind = TOA_JIT_RESIDUAL, const std::string& plus_body = std::string(), int x_scalars = 0,
+              int diff = TOA_DIFF_DEFAULT, float diff_h = 0.f)
       : ctx_(&ctx), n_(n), kR_(residuals_per_item), kD_(item_scalars), kH_(header_scalars),
-        xdim_(manifold == TOA_MANIFOLD_SE3 ? 12 : (manifold == TOA_MANIFOLD_USER ? x_scalars : n)) {
+        xdim_(manifold == TOA_MANIFOLD_SE3 ? 12 : (manifold == TOA_MANIFOLD_USER ? x_scalars : n)), diff_(diff) {
     std::vector<char> log(1 << 16);
     toa_jit_spec spec{};
     spec.dtype = dtype_of<Scalar>(); spec.num_params = n; spec.residuals_per_item = residuals_per_item;
     spec.scalars_per_item = item_scalars; spec.header_scalars = header_scalars; spec.manifold = manifold; spec.kind = kind;
     if (manifold == TOA_MANIFOLD_USER) { spec.x_scalars = x_scalars; spec.plus_body = plus_body.c_str(); }
+    spec.diff = diff; spec.diff_h = diff_h;
     const int rc = toa_model_compile_ex(ctx.get(), &spec, body.c_str(), &h_, log.data(), log.size());
     log_ = log.data();
     check(rc);
@@ -378,6 +388,7 @@ class JitResidual {
   int item_scalars() const { return kD_; }
   int header_scalars() const { return kH_; }
   int xdim() const { return xdim_; }   // stored scalars of x per problem (12 for an SE3 pose)
+  int diff() const { return diff_; }   // TOA_DIFF_*
   // What the run-time build came out as (toa_jit_model_stats): resident workgroups per compute unit, LDS per workgroup, vector
   // registers per lane, scratch bytes per lane — a body heavy enough to spill or to drop to one workgroup shows up here.
   struct BuildStats { int wg_per_cu = 0, lds_bytes_per_wg = 0, num_regs = 0, scratch_bytes = 0; };
@@ -390,7 +401,7 @@ class JitResidual {
  private:
   const Context* ctx_;
   toa_jit_model h_ = nullptr;
-  int n_, kR_, kD_, kH_, xdim_;
+  int n_, kR_, kD_, kH_, xdim_, diff_;
   std::string log_;
 };
 template <typename Scalar>
@@ -409,6 +420,7 @@ class JitModel : public LossTag {
   const Scalar* data() const { return data_.data(); }
   const Context& ctx() const { return res_->ctx(); }
   toa_jit_model jit_handle() const { return res_->handle(); }
+  int diff() const { return res_->diff(); }
 
  private:
   const JitResidual<Scalar>* res_;
@@ -462,6 +474,11 @@ BatchOutput Optimize(std::vector<Scalar>& x, const Cost& cost, const Options& op
   if (gd && options.has_host_controls())
     throw std::invalid_argument("tinyopt_amd::Optimize: GradientDescent runs as one launch per solve: stop callbacks, max_duration_ms "
                                 "and the log line are not supported on this path");
+  if constexpr (detail::is_jit<Cost>::value) {
+    if (cost.diff() != TOA_DIFF_DEFAULT && options.has_host_controls())
+      throw std::invalid_argument("tinyopt_amd::Optimize: a numerically differentiated model runs as one launch per solve: stop callbacks, "
+                                  "max_duration_ms and the log line are not supported (it has no stepping form)");
+  }
   if (options.has_host_controls()) {
     return OptimizeWithHostControls(x, cost, options, history);   // (run-time models too: toa_jit_lm_begin / step / stop)
   }
@@ -509,6 +526,43 @@ BatchOutput Optimize(std::vector<Scalar>& x, const Cost& cost, const Options& op
   if (history) { get(out.errs, errs); get(out.deltas2, d2); get(out.successes, succ); }
   return out;
 }
+
+// diff::CheckGradient / diff::CheckResidualsGradient (diff/gradient_check.h:50-220) for a bound run-time model of any kind, at
+// x [P][n]: the model's own derivatives against finite differences of its residuals (cost terms) with step eps / 10 — g = J^T r and,
+// with check_H, H = J^T J for residual kinds; g for cost kinds.  eps <= 0: the reference's default (1e-2 for float, 1e-5 for double).
+struct GradientCheck {
+  std::vector<int32_t> ok;                    // [P]
+  std::vector<double> max_dist_g, max_dist_H; // [P]
+  bool all() const { for (int32_t v : ok) if (!v) return false; return true; }
+  explicit operator bool() const { return all(); }
+};
+namespace diff {
+template <typename Scalar>
+GradientCheck CheckGradient(const JitModel<Scalar>& model, const std::vector<Scalar>& x, double eps = 0.0, Method method = kCentral,
+                            bool check_H = true) {
+  const int64_t P = model.P();
+  if (int64_t(x.size()) != P * model.xdim())
+    throw std::invalid_argument("tinyopt_amd::diff::CheckGradient: x must hold P * (parameters per problem) scalars");
+  const Context& ctx = model.ctx();
+  DeviceBuffer<Scalar> dx(ctx, x.size());
+  dx.upload(x.data());
+  DeviceBuffer<double> dist(ctx, size_t(P) * 2);
+  DeviceBuffer<int32_t> ok(ctx, size_t(P));
+  apply_loss(model);
+  check(toa_jit_check_gradient(ctx.get(), model.jit_handle(), model.items(), P, model.data(), dx.data(), eps, to_pod(method), check_H ? 1 : 0,
+                               dist.data(), ok.data()));
+  check(toa_synchronize(ctx.get()));
+  GradientCheck out;
+  out.ok.resize(size_t(P));
+  ok.download(out.ok.data());
+  std::vector<double> d(size_t(P) * 2);
+  dist.download(d.data());
+  out.max_dist_g.resize(size_t(P));
+  out.max_dist_H.resize(size_t(P));
+  for (size_t p = 0; p < size_t(P); ++p) { out.max_dist_g[p] = d[2 * p]; out.max_dist_H[p] = d[2 * p + 1]; }
+  return out;
+}
+}  // namespace diff
 
 // The reference's class / stepping form (`lm::Optimizer<H_t> optimizer(options)`; `optimizer.Step(x, acc, out)` one loop
 // pass at a time; `optimizer(x, f, max_iters)` — include/tinyopt/optimizers/optimizer.h:199,331-539) for a batch.

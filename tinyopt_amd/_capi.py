@@ -59,6 +59,7 @@ class ToaResults(C.Structure):
 
 # every symbol include/tinyopt_amd.h declares: name -> (restype, argtypes)
 ABI_VERSION = 7   # include/tinyopt_amd.h TOA_ABI_VERSION
+DIFF_DEFAULT, DIFF_NUM_FORWARD, DIFF_NUM_CENTRAL, DIFF_NUM_FAST_CENTRAL = 0, 1, 2, 3   # TOA_DIFF_* (added under version 7)
 
 
 class ToaTuning(C.Structure):   # include/tinyopt_amd.h toa_tuning
@@ -70,7 +71,7 @@ class ToaTuning(C.Structure):   # include/tinyopt_amd.h toa_tuning
 class ToaJitSpec(C.Structure):   # include/tinyopt_amd.h toa_jit_spec
     _fields_ = [("dtype", C.c_int32), ("num_params", C.c_int32), ("residuals_per_item", C.c_int32), ("scalars_per_item", C.c_int32),
                 ("header_scalars", C.c_int32), ("manifold", C.c_int32), ("kind", C.c_int32), ("x_scalars", C.c_int32),
-                ("plus_body", C.c_char_p), ("reserved", C.c_int32 * 6)]
+                ("plus_body", C.c_char_p), ("diff", C.c_int32), ("diff_h", C.c_float), ("reserved", C.c_int32 * 4)]
 
 
 class ToaGdOptions(C.Structure):   # include/tinyopt_amd.h toa_gd_options (Options::GD, options.h:147-154)
@@ -132,6 +133,7 @@ PROTOTYPES = {
     "toa_model_destroy": (C.c_int, [_P]),
     "toa_jit_lm_run": (C.c_int, [_P, _P, C.c_int, C.c_int64, _P, _P, C.POINTER(ToaOptions), C.POINTER(ToaResults), _P]),
     "toa_jit_accumulate": (C.c_int, [_P, _P, C.c_int, C.c_int64, _P, _P, C.c_int, _P, _P, _P, _P]),
+    "toa_jit_check_gradient": (C.c_int, [_P, _P, C.c_int, C.c_int64, _P, _P, C.c_double, C.c_int, C.c_int, _P, _P]),
     "toa_gd_options_default": (None, [C.POINTER(ToaGdOptions)]),
     "toa_jit_gd_run": (C.c_int, [_P, _P, C.c_int, C.c_int64, _P, _P, C.POINTER(ToaOptions), C.POINTER(ToaGdOptions), C.POINTER(ToaResults), _P]),
     "toa_jit_lm_run_split": (C.c_int, [_P, _P, C.c_int, C.c_int64, _P, _P, C.POINTER(ToaOptions), C.POINTER(ToaResults), _P, C.c_int]),

@@ -497,15 +497,23 @@ class JitResidual:
                                    "c = log(S(1) + exp(-p[12] * z));", n=12, item_scalars=13, kind="cost", dtype=torch.float32)
 
       * ``kind="cost_grad"`` — ``f(x, grad) -> scalar`` (tests/unconstrained.cpp:19-42): ``c`` on plain T and, inside
-        ``if (want_grad) { ... }``, the item's own gradient added to ``G[a]``."""
+        ``if (want_grad) { ... }``, the item's own gradient added to ``G[a]``.
+
+    Numerical differentiation (the reference's diff/num_diff.h: ``NumEval`` / ``CreateNumDiffFunc1/2``) — ``diff="forward"``,
+    ``"central"`` or ``"fast_central"`` with step ``diff_h`` (0 = FloatEpsilon: 1e-4 in float32, 1e-7 in float64) differentiates a
+    ``kind="residual"`` or ``kind="cost"`` body by finite differences instead of Jets: the body is only ever instantiated on the
+    plain scalar type (``S`` = ``T``), so it need not be generic (tests/diff.cpp:113-132).  Euclidean parameters; 2 n + 1
+    evaluations of the body per item and pass; no ``splits`` and no host controls (stop callbacks, max_duration_ms, the log line).
+    ``CheckGradient(model, x)`` compares the derivatives of ANY model with those differences."""
 
     MANIFOLDS = {"euclid": 0, "se3": 1, "user": 2}
     KINDS = {"residual": 0, "accumulate": 1, "cost": 2, "cost_grad": 3}
     COST_KINDS = ("cost", "cost_grad")
+    DIFFS = {"ad": 0, "forward": 1, "central": 2, "fast_central": 3}
 
     def __init__(self, body: str, n: int, item_scalars: int, residuals_per_item: int = 1, header_scalars: int = 0,
                  dtype: torch.dtype = torch.float64, ctx: Optional["Context"] = None, manifold: str = "euclid", kind: str = "residual",
-                 plus_body: Optional[str] = None, x_scalars: int = 0):
+                 plus_body: Optional[str] = None, x_scalars: int = 0, diff: str = "ad", diff_h: float = 0.0):
         """Round 5 — ``manifold="user"``: the caller's own parameter container (the reference's traits::params_trait<T>, traits.h:103-359).
         x is stored as ``x_scalars`` scalars per problem ([P, x_scalars]), ``n`` is the dimension of its tangent and ``plus_body``
         is the body of ``template <class S> void plus(const T* x, const S* d, S* xp)``: xp = x (+) d, written over the scalar type
@@ -517,6 +525,9 @@ class JitResidual:
         self.manifold, self.kind = manifold, kind
         if kind not in self.KINDS:
             raise ValueError(f"unknown kind {kind!r}; one of {sorted(self.KINDS)}")
+        if diff not in self.DIFFS:
+            raise ValueError(f"unknown diff {diff!r}; one of {sorted(self.DIFFS)}")
+        self.diff, self.diff_h = diff, float(diff_h)
         self.xdim = 12 if manifold == "se3" else (int(x_scalars) if manifold == "user" else self.n)
         self._h = C.c_void_p()
         log = C.create_string_buffer(1 << 16)
@@ -524,6 +535,7 @@ class JitResidual:
         spec.dtype, spec.num_params, spec.residuals_per_item = _dtype_code(dtype), self.n, self.kR
         spec.scalars_per_item, spec.header_scalars = self.kD, self.kH
         spec.manifold, spec.kind = self.MANIFOLDS[manifold], self.KINDS[kind]
+        spec.diff, spec.diff_h = self.DIFFS[diff], self.diff_h
         if manifold == "user":
             if not plus_body or int(x_scalars) < 1:
                 raise ValueError('manifold="user" needs plus_body (the body of x (+) d) and x_scalars')
@@ -864,6 +876,9 @@ def Optimize(x: torch.Tensor, cost, options: Optional[Options] = None, *, histor
                                        cost.obs_cam.data_ptr(), cost.obs_pt.data_ptr(), cost.obs_uv.data_ptr(), x.data_ptr(),
                                        C.byref(pod), C.byref(res), out.counters.data_ptr(), float(options.max_duration_ms or 0.0)))
         return out
+    if isinstance(cost, JitModel) and cost.res.diff != "ad" and (options.has_host_controls() or splits is not None):
+        raise ValueError("a numerically differentiated model (diff=...) runs as one launch per solve: no stop callbacks, max_duration_ms, "
+                         "log line or splits (it has no stepping and no row-split form)")
     if isinstance(cost, JitModel) and cost.res.kind in JitResidual.COST_KINDS and options.solver_type == Options.GradientDescent:
         return _optimize_gd(x, cost, options, history, ctx, out, splits, zero_counters)
     if isinstance(cost, JitModel):
@@ -944,6 +959,8 @@ class Optimizer:
                  ctx: Optional[Context] = None):
         self.options = options or Options()
         _check_call(x, cost)
+        if isinstance(cost, JitModel) and cost.res.diff != "ad":
+            raise ValueError("a numerically differentiated model (diff=...) has no stepping form")
         self.x, self.cost = x, cost
         self.ctx = ctx or default_context(x.device.index)
         self.pod = self.options.to_pod()
@@ -1155,6 +1172,43 @@ def accumulate(cost, x: torch.Tensor, want_grad: bool = True, ctx: Optional[Cont
                                  x.data_ptr(), int(want_grad), g.data_ptr() if want_grad else None,
                                  H.data_ptr() if want_grad else None, c.data_ptr(), nres.data_ptr()))
     return g, H, c, nres
+
+
+class GradientCheck:
+    """What ``CheckGradient`` found, per problem: ``ok`` (bool [P]), ``max_dist_g`` / ``max_dist_H`` (float64 [P])."""
+
+    def __init__(self, ok: torch.Tensor, max_dist_g: torch.Tensor, max_dist_H: torch.Tensor, eps: float):
+        self.ok, self.max_dist_g, self.max_dist_H, self.eps = ok, max_dist_g, max_dist_H, eps
+
+    def all(self) -> bool:
+        return bool(self.ok.all())
+
+    def __bool__(self) -> bool:
+        return self.all()
+
+
+def CheckGradient(model: "JitModel", x: torch.Tensor, eps: Optional[float] = None, method: str = "central", check_H: bool = True,
+                  ctx: Optional[Context] = None) -> GradientCheck:
+    """``diff::CheckGradient`` / ``diff::CheckResidualsGradient`` (diff/gradient_check.h) for a bound run-time model of any kind, at
+    x [P, n]: the model's own derivatives against finite differences of its residuals (or cost terms) with step eps / 10.
+    Residual kinds compare g = J^T r and, with ``check_H``, H = J^T J; cost kinds compare g.  ``eps`` None: the reference's default
+    (1e-2 in float32, 1e-5 in float64).  The first check of a model with a (method, eps) compiles its numeric twin (then cached)."""
+    if not isinstance(model, JitModel):
+        raise TypeError("CheckGradient takes a bound run-time model (JitResidual.bind)")
+    if method not in ("forward", "central", "fast_central"):
+        raise ValueError(f"unknown method {method!r}; one of 'forward', 'central', 'fast_central'")
+    _check_call(x, model)
+    ctx = ctx or default_context(x.device.index)
+    P = x.shape[0]
+    dist = torch.zeros(P, 2, dtype=torch.float64, device=x.device)
+    ok = torch.zeros(P, dtype=torch.int32, device=x.device)
+    _apply_loss(ctx, model)
+    e = 0.0 if eps is None else float(eps)
+    check(ctx.lib.toa_jit_check_gradient(ctx.h, model.res._h, model.items, P, model.packed.data_ptr(), x.data_ptr(), e,
+                                         JitResidual.DIFFS[method], int(bool(check_H)), dist.data_ptr(), ok.data_ptr()))
+    if eps is None:
+        e = 1e-2 if x.dtype == torch.float32 else 1e-5
+    return GradientCheck(ok != 0, dist[:, 0], dist[:, 1], e)
 
 
 def solve_damped(H: torch.Tensor, g: torch.Tensor, scale: float = 1.0, ctx: Optional[Context] = None):

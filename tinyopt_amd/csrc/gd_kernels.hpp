@@ -27,6 +27,7 @@
 #include "gd_device.hpp"
 #include "jet.hpp"
 #include "wave_utils.hpp"
+#include "num_diff.hpp"   // NumCostFunctor: a cost body differentiated by finite differences (toa_jit_spec::diff)
 
 namespace toa {
 

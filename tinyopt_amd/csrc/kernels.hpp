@@ -15,6 +15,7 @@
 //   models_jet.hpp       JetModel (n <= 12), functor traits, built-in functors  -> row_model.hpp (13 <= n <= 63)
 //   fused_kernels.hpp    lm_fused_kernel, accumulate / solve_damped / inv_cov seams
 //   wide_kernels.hpp     row-split, stepping-state, team and persistent kernels
+//   num_diff.hpp         finite-difference functors of run-time models, the gradient checker's comparison
 //   host_launch.hpp      handle, launchers (host only: left out of run-time builds)
 #pragma once
 #include <hip/hip_runtime.h>
@@ -25,6 +26,7 @@
 #include "../../include/tinyopt_amd.h"
 #endif
 #include "wide_kernels.hpp"
+#include "num_diff.hpp"   // NumRowFunctor / NumCostFunctor: finite differences of run-time functors (toa_jit_spec::diff), check_gradient_kernel
 #ifndef __HIPCC_RTC__
 #include "host_launch.hpp"
 #endif

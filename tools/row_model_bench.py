@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
-"""The headline shape (n = 50, m = 2000, fp32) through four doors: the compiled-in DenseRow family, the same residual with its
+"""The headline shape (n = 50, m = 2000, fp32) through five doors: the compiled-in DenseRow family, the same residual with its
 Jacobian supplied as TEXT (RowModel over the user's functor), as text WITHOUT a Jacobian (row-per-lane chunked Jets), and the
-compiled-in AD model.  usage: python tools/row_model_bench.py [P] [n] [m] [f32|f64]"""
+compiled-in AD model — and as text differentiated by central differences ("text num").  usage: python tools/row_model_bench.py [P] [n] [m] [f32|f64]"""
 import os
 import sys
 
@@ -47,7 +47,10 @@ def main():
     mb, ab = narrow_bodies(n) if n <= 12 else (manual_body(n), ad_body(n))
     models = [("compiled-in", ta.DenseRow.from_arrays(A, b)),
               ("text+J", ta.JitResidual(mb, n=n, item_scalars=n + 1, dtype=dt, kind="accumulate").bind(items)),
-              ("text AD", ta.JitResidual(ab, n=n, item_scalars=n + 1, dtype=dt).bind(items))]
+              ("text AD", ta.JitResidual(ab, n=n, item_scalars=n + 1, dtype=dt).bind(items)),
+              # C4 as text, central differences (csrc/num_diff.hpp): 2 n + 1 evaluations of the body per item against the
+              # n / 12 Jet evaluations of "text AD" — ROWBENCH_ONLY="text AD,text num" puts the two side by side
+              ("text num", ta.JitResidual(ab, n=n, item_scalars=n + 1, dtype=dt, diff="central").bind(items))]
     if n in (12, 50):
         models.append(("built-in AD", ta.DenseRowAD(A, b)))
     only = os.environ.get("ROWBENCH_ONLY")

@@ -9,7 +9,11 @@ Two things the entries do NOT have in common, pinned as they are:
   * the stepping form of a run-time model (toa_jit_lm_begin / _step / _stop) has no max_iters bound — the host drives its loop —
     so max_iters = 70000 is accepted there (one begin, step, stop on two 8-row problems);
   * P = 0 returns TOA_OK whatever the data pointers are on the run-time-model entries only: toa_lm_run, toa_ba_run and
-    toa_ba_lists_run test their pointers first ("<entry>: null pointer", "DenseRow: data pointer is null")."""
+    toa_ba_lists_run test their pointers first ("<entry>: null pointer", "DenseRow: data pointer is null").
+
+The second half pins what the compiled-in entries refuse about the ROUTE of a call (csrc/small_route.hpp and the checks of
+csrc/capi.hip in front of it): a row-split of a family that has none, the natural layout's missing forms, a parameter count
+without an instance, a stepping call without its state or stop block, a dtype that is neither TOA_F32 nor TOA_F64."""
 import ctypes as C
 
 import pytest
@@ -172,3 +176,85 @@ def test_empty_batch(env, entry):
     else:
         text = "DenseRow: data pointer is null" if entry == "toa_lm_run" else f"{entry}: null pointer"
         env.refused(entry, o, r, text, batch=0, null_data=True)
+
+
+# ---- the routing refusals of the compiled-in entries (toa_lm_run / _run_split / _begin / _stop, toa_accumulate and the two
+# ---- per-element helpers): code and exact text; every one is decided before anything is launched ----
+E_UNSUPPORTED = -4
+DTYPE_TEXT = "dtype must be TOA_F32 or TOA_F64"
+ROW_SPLIT_TEXT = "row-split execution is available for DenseRow and SE3Reproj"
+
+
+def compiled_in(env, entry, model, n, *, dtype=None, splits=None, state=True, stop_request=True):
+    """`entry` of the compiled-in families on the file's buffers (m = ITEMS, P problems)."""
+    lib, h, k = env.lib, env.ctx.h, env.capi
+    dtype = k.F64 if dtype is None else dtype
+    o, r = env.options("toa_lm_run"), env.results()
+    head = (h, model, dtype, n, ITEMS, P, env.data.data_ptr(), env.x.data_ptr(), C.byref(o), C.byref(r))
+    cnt, st = env.counters.data_ptr(), (env.state.data_ptr() if state else None)
+    if entry == "toa_lm_run":
+        return lib.toa_lm_run(*head, cnt)
+    if entry == "toa_lm_run_split":
+        return lib.toa_lm_run_split(*head, cnt, splits)
+    if entry == "toa_lm_begin":
+        return lib.toa_lm_begin(*head, st)
+    if entry == "toa_lm_stop":
+        return lib.toa_lm_stop(*head, cnt, st, env.stop_request.data_ptr() if stop_request else None)
+    raise KeyError(entry)
+
+
+def refused_with(env, rc, code, text):
+    assert rc == code, (rc, env.lib.toa_last_error())
+    assert env.lib.toa_last_error().decode() == text
+
+
+@pytest.mark.parametrize("model,n", [("MODEL_CIRCLE_FIT", 3), ("MODEL_DENSE_ROW_AD", 12)])
+@pytest.mark.parametrize("splits", [0, 1])
+def test_row_split_of_a_family_without_one(env, model, n, splits):
+    refused_with(env, compiled_in(env, "toa_lm_run_split", getattr(env.capi, model), n, splits=splits), E_UNSUPPORTED, ROW_SPLIT_TEXT)
+
+
+def test_row_split_negative_splits(env):
+    refused_with(env, compiled_in(env, "toa_lm_run_split", env.capi.MODEL_DENSE_ROW, N, splits=-1), E_ARG,
+                 "toa_lm_run_split: splits must be >= 0 (0 = choose automatically)")
+
+
+@pytest.mark.parametrize("splits", [0, 2])
+def test_natural_layout_has_no_row_split_form(env, splits):
+    refused_with(env, compiled_in(env, "toa_lm_run_split", env.capi.MODEL_DENSE_ROW_NATURAL, N, splits=splits), E_UNSUPPORTED,
+                 "TOA_MODEL_DENSE_ROW_NATURAL: no row-split form")
+
+
+def test_natural_layout_stepping_form_below_64(env):
+    refused_with(env, compiled_in(env, "toa_lm_begin", env.capi.MODEL_DENSE_ROW_NATURAL, 6), E_UNSUPPORTED,
+                 "TOA_MODEL_DENSE_ROW_NATURAL: the stepping form starts at n = 64 (use TOA_MODEL_DENSE_ROW below)")
+
+
+def test_dense_row_ad_at_an_n_without_an_instance(env):
+    refused_with(env, compiled_in(env, "toa_lm_run", env.capi.MODEL_DENSE_ROW_AD, 13), E_UNSUPPORTED,
+                 "DenseRowAD: instantiated for n = 12 and n = 50 (a functor's parameter count is a compile-time constant)")
+
+
+def test_begin_without_a_state_block(env):
+    refused_with(env, compiled_in(env, "toa_lm_begin", env.capi.MODEL_DENSE_ROW, N, state=False), E_ARG,
+                 "toa_lm_begin / toa_lm_step: state_dev is null")
+
+
+def test_stop_without_a_stop_request(env):
+    refused_with(env, compiled_in(env, "toa_lm_stop", env.capi.MODEL_DENSE_ROW, N, stop_request=False), E_ARG,
+                 "toa_lm_stop: stop_request_dev is null")
+
+
+@pytest.mark.parametrize("entry", ["toa_lm_run", "toa_accumulate", "toa_robust_norm", "toa_jet_eval"])
+def test_bad_dtype(env, entry):
+    lib, h, bad = env.lib, env.ctx.h, 7
+    d, x, f = env.data.data_ptr(), env.x.data_ptr(), env.final.data_ptr()
+    if entry == "toa_lm_run":
+        rc = compiled_in(env, entry, env.capi.MODEL_DENSE_ROW, N, dtype=bad)
+    elif entry == "toa_accumulate":
+        rc = lib.toa_accumulate(h, env.capi.MODEL_DENSE_ROW, bad, N, ITEMS, P, d, x, 0, None, None, f, None)
+    elif entry == "toa_robust_norm":
+        rc = lib.toa_robust_norm(h, 1, bad, P, d, 1.0, x, f)
+    else:
+        rc = lib.toa_jet_eval(h, 0, bad, P, d, d, x)
+    refused_with(env, rc, E_ARG, ("toa_robust_norm: " if entry == "toa_robust_norm" else "") + DTYPE_TEXT)

@@ -2,6 +2,8 @@
 // per-(dtype, block count) kernel instantiations (inst.hip), and the data-format callers either side
 // of the path (pack / synth kernels).  gfx950 (MI355X, CDNA4) only.
 #include "kernels.hpp"
+#include "inst.hpp"
+#include "small_route.hpp"
 
 namespace toa {
 
@@ -166,61 +168,6 @@ __global__ void dense_row_synth_kernel(T* __restrict__ out, T* __restrict__ x0, 
 
 using namespace toa;
 
-int toa_inst_solve_0_0(int npad, toa_handle h, int n, int64_t P, const void* H, const void* g, double scale, void* dx, int32_t* ok);
-int toa_inst_fused_0_1(int thin, toa_handle h, const toa::FusedParams& prm);
-int toa_inst_accumulate_0_1(int thin, toa_handle h, int n, int m, int64_t P, const void* data, const void* x, int want_grad, void* g, void* H, double* cost, int32_t* nres);
-int toa_inst_fused_0_2(int thin, toa_handle h, const toa::FusedParams& prm);
-int toa_inst_accumulate_0_2(int thin, toa_handle h, int n, int m, int64_t P, const void* data, const void* x, int want_grad, void* g, void* H, double* cost, int32_t* nres);
-int toa_inst_fused_0_3(int thin, toa_handle h, const toa::FusedParams& prm);
-int toa_inst_accumulate_0_3(int thin, toa_handle h, int n, int m, int64_t P, const void* data, const void* x, int want_grad, void* g, void* H, double* cost, int32_t* nres);
-int toa_inst_fused_0_4(int thin, toa_handle h, const toa::FusedParams& prm);
-int toa_inst_accumulate_0_4(int thin, toa_handle h, int n, int m, int64_t P, const void* data, const void* x, int want_grad, void* g, void* H, double* cost, int32_t* nres);
-int toa_inst_solve_1_0(int npad, toa_handle h, int n, int64_t P, const void* H, const void* g, double scale, void* dx, int32_t* ok);
-int toa_inst_fused_1_1(int thin, toa_handle h, const toa::FusedParams& prm);
-int toa_inst_accumulate_1_1(int thin, toa_handle h, int n, int m, int64_t P, const void* data, const void* x, int want_grad, void* g, void* H, double* cost, int32_t* nres);
-int toa_inst_fused_1_2(int thin, toa_handle h, const toa::FusedParams& prm);
-int toa_inst_accumulate_1_2(int thin, toa_handle h, int n, int m, int64_t P, const void* data, const void* x, int want_grad, void* g, void* H, double* cost, int32_t* nres);
-int toa_inst_fused_1_3(int thin, toa_handle h, const toa::FusedParams& prm);
-int toa_inst_accumulate_1_3(int thin, toa_handle h, int n, int m, int64_t P, const void* data, const void* x, int want_grad, void* g, void* H, double* cost, int32_t* nres);
-int toa_inst_fused_1_4(int thin, toa_handle h, const toa::FusedParams& prm);
-int toa_inst_accumulate_1_4(int thin, toa_handle h, int n, int m, int64_t P, const void* data, const void* x, int want_grad, void* g, void* H, double* cost, int32_t* nres);
-
-int toa_inst_misc_fused_0_0(int model, int npad, toa_handle h, const toa::FusedParams& prm);
-int toa_inst_misc_fused_1_0(int model, int npad, toa_handle h, const toa::FusedParams& prm);
-int toa_inst_misc_accumulate_0_0(int model, int npad, toa_handle h, int n, int m, int64_t P, const void* data, const void* x, int want_grad, void* g, void* H, double* cost, int32_t* nres);
-int toa_inst_misc_accumulate_1_0(int model, int npad, toa_handle h, int n, int m, int64_t P, const void* data, const void* x, int want_grad, void* g, void* H, double* cost, int32_t* nres);
-
-int toa_inst_misc_wide_0_0(int model, toa_handle h, const toa::FusedParams& prm, int splits);
-int toa_inst_wide_0_1(int thin, toa_handle h, const toa::FusedParams& prm, int splits);
-int toa_inst_wide_0_2(int thin, toa_handle h, const toa::FusedParams& prm, int splits);
-int toa_inst_wide_0_3(int thin, toa_handle h, const toa::FusedParams& prm, int splits);
-int toa_inst_wide_0_4(int thin, toa_handle h, const toa::FusedParams& prm, int splits);
-int toa_inst_misc_wide_1_0(int model, toa_handle h, const toa::FusedParams& prm, int splits);
-int toa_inst_wide_1_1(int thin, toa_handle h, const toa::FusedParams& prm, int splits);
-int toa_inst_wide_1_2(int thin, toa_handle h, const toa::FusedParams& prm, int splits);
-int toa_inst_wide_1_3(int thin, toa_handle h, const toa::FusedParams& prm, int splits);
-int toa_inst_wide_1_4(int thin, toa_handle h, const toa::FusedParams& prm, int splits);
-
-int toa_inst_narrow_fused_0_0(int n, toa_handle h, const toa::FusedParams& prm);
-int toa_inst_narrow_fused_1_0(int n, toa_handle h, const toa::FusedParams& prm);
-int toa_inst_narrow_accumulate_1_0(toa_handle h, int n, int m, int64_t P, const void* data, const void* x, int want_grad, void* g, void* H, double* cost, int32_t* nres);
-// the instances of inst.hip's narrow routes of TOA_MODEL_DENSE_ROW (JetModel / RowModel over the packed rows)
-static bool dense_row_lane_route(int dtag, int n, bool robust) {
-  if (n >= 1 && n <= (dtag == 0 ? 11 : 5)) return true;      // narrow blocks, with or without an M-estimator
-  if (dtag == 1 && n == 6) return true;                      // (fp64 n = 6: JetModel without the estimator branch for L2, RowModel with a loss)
-  if (!robust) return false;
-  return n == 12 || n == 50;                                  // the BASELINE shapes with an M-estimator on the handle
-}
-int toa_inst_narrow_accumulate_0_0(toa_handle h, int n, int m, int64_t P, const void* data, const void* x, int want_grad, void* g, void* H, double* cost, int32_t* nres);
-int toa_inst_jetrow_fused_0_0(int n, toa_handle h, const toa::FusedParams& prm);
-int toa_inst_jetrow_fused_1_0(int n, toa_handle h, const toa::FusedParams& prm);
-int toa_inst_jetrow_wide_0_0(int n, toa_handle h, const toa::FusedParams& prm);
-int toa_inst_jetrow_wide_1_0(int n, toa_handle h, const toa::FusedParams& prm);
-int toa_inst_jetrow_accumulate_0_0(toa_handle h, int n, int m, int64_t P, const void* data, const void* x, int want_grad, void* g, void* H, double* cost, int32_t* nres);
-int toa_inst_jetrow_accumulate_1_0(toa_handle h, int n, int m, int64_t P, const void* data, const void* x, int want_grad, void* g, void* H, double* cost, int32_t* nres);
-int toa_inst_inv_cov_0_0(int npad, toa_handle h, int n, int64_t P, const void* H, void* C, int32_t* ok);
-int toa_inst_inv_cov_1_0(int npad, toa_handle h, int n, int64_t P, const void* H, void* C, int32_t* ok);
-
 static thread_local std::string g_err;
 int toa_fail(int code, const std::string& msg) {
   g_err = msg;
@@ -228,49 +175,15 @@ int toa_fail(int code, const std::string& msg) {
 }
 static int fail(int code, const std::string& msg) { return toa_fail(code, msg); }
 
-int toa_inst_fused(int dtag, int nbm, int thin, toa_handle h, const FusedParams& prm) {
-  switch (dtag * 8 + nbm) {
-    case 1: return toa_inst_fused_0_1(thin, h, prm); case 2: return toa_inst_fused_0_2(thin, h, prm);
-    case 3: return toa_inst_fused_0_3(thin, h, prm); case 4: return toa_inst_fused_0_4(thin, h, prm);
-    case 9: return toa_inst_fused_1_1(thin, h, prm); case 10: return toa_inst_fused_1_2(thin, h, prm);
-    case 11: return toa_inst_fused_1_3(thin, h, prm); case 12: return toa_inst_fused_1_4(thin, h, prm);
-  }
-  return fail(TOA_E_ARG, "bad block count");
+// the pre-instantiated kernels' entry points (inst.hpp), by dtag
+static const toa_inst_table kInst[2] = {TOA_INST_TABLE(0), TOA_INST_TABLE(1)};
+static int dtag_of(int dtype) { return dtype == TOA_F32 ? 0 : 1; }
+static int npad_of(int n) { return 16 * ((n + 15) / 16); }
+static bool dtype_ok(int dtype) { return dtype == TOA_F32 || dtype == TOA_F64; }
+static int check_dtype(int dtype, const char* who = "") {
+  return dtype_ok(dtype) ? TOA_OK : fail(TOA_E_ARG, std::string(who) + "dtype must be TOA_F32 or TOA_F64");
 }
-int toa_inst_accumulate(int dtag, int nbm, int thin, toa_handle h, int n, int m, int64_t P, const void* data,
-                        const void* x, int want_grad, void* g, void* H, double* cost, int32_t* nres) {
-#define TOA_A(f) return f(thin, h, n, m, P, data, x, want_grad, g, H, cost, nres)
-  switch (dtag * 8 + nbm) {
-    case 1: TOA_A(toa_inst_accumulate_0_1); case 2: TOA_A(toa_inst_accumulate_0_2);
-    case 3: TOA_A(toa_inst_accumulate_0_3); case 4: TOA_A(toa_inst_accumulate_0_4);
-    case 9: TOA_A(toa_inst_accumulate_1_1); case 10: TOA_A(toa_inst_accumulate_1_2);
-    case 11: TOA_A(toa_inst_accumulate_1_3); case 12: TOA_A(toa_inst_accumulate_1_4);
-  }
-#undef TOA_A
-  return fail(TOA_E_ARG, "bad block count");
-}
-int toa_inst_wide(int dtag, int model, int nbm, int thin, toa_handle h, const FusedParams& prm, int splits) {
-  if (model != TOA_MODEL_DENSE_ROW)
-    return dtag == 0 ? toa_inst_misc_wide_0_0(model, h, prm, splits) : toa_inst_misc_wide_1_0(model, h, prm, splits);
-  switch (dtag * 8 + nbm) {
-    case 1: return toa_inst_wide_0_1(thin, h, prm, splits); case 2: return toa_inst_wide_0_2(thin, h, prm, splits);
-    case 3: return toa_inst_wide_0_3(thin, h, prm, splits); case 4: return toa_inst_wide_0_4(thin, h, prm, splits);
-    case 9: return toa_inst_wide_1_1(thin, h, prm, splits); case 10: return toa_inst_wide_1_2(thin, h, prm, splits);
-    case 11: return toa_inst_wide_1_3(thin, h, prm, splits); case 12: return toa_inst_wide_1_4(thin, h, prm, splits);
-  }
-  return fail(TOA_E_ARG, "bad block count");
-}
-int toa_inst_misc_fused(int dtag, int model, int npad, toa_handle h, const FusedParams& prm) {
-  return dtag == 0 ? toa_inst_misc_fused_0_0(model, npad, h, prm) : toa_inst_misc_fused_1_0(model, npad, h, prm);
-}
-int toa_inst_misc_accumulate(int dtag, int model, int npad, toa_handle h, int n, int m, int64_t P, const void* data,
-                             const void* x, int want_grad, void* g, void* H, double* cost, int32_t* nres) {
-  return dtag == 0 ? toa_inst_misc_accumulate_0_0(model, npad, h, n, m, P, data, x, want_grad, g, H, cost, nres)
-                   : toa_inst_misc_accumulate_1_0(model, npad, h, n, m, P, data, x, want_grad, g, H, cost, nres);
-}
-int toa_inst_inv_cov(int dtag, int npad, toa_handle h, int n, int64_t P, const void* H, void* C, int32_t* ok) {
-  return dtag == 0 ? toa_inst_inv_cov_0_0(npad, h, n, P, H, C, ok) : toa_inst_inv_cov_1_0(npad, h, n, P, H, C, ok);
-}
+
 int toa_large_solve(toa_handle h, int dtype, int n, int64_t P, const void* H, const void* g, double scale, void* dx, int32_t* ok);
 int toa_large_inv_cov(toa_handle h, int dtype, int n, int64_t P, const void* H, void* C, int32_t* ok);
 int toa_large_lm_run(toa_handle h, int dtype, int n, int m, int64_t P, const void* data, void* x, const toa_options* options,
@@ -282,11 +195,6 @@ int toa_large_lm_step(toa_handle h, int dtype, int n, int m, int64_t P, const vo
 int toa_large_step_log(toa_handle h, int dtype, int n, int64_t P, const void* state, double* lambda, int32_t* nres, int32_t* ninl);
 int toa_large_step_info(toa_handle h, int dtype, int n, int64_t P, const void* state, double* err, double* dx2, double* g2,
                         void* dx_out, void* g_out);
-int toa_inst_solve(int dtag, int npad, toa_handle h, int n, int64_t P, const void* H, const void* g, double scale,
-                   void* dx, int32_t* ok) {
-  return dtag == 0 ? toa_inst_solve_0_0(npad, h, n, P, H, g, scale, dx, ok)
-                   : toa_inst_solve_1_0(npad, h, n, P, H, g, scale, dx, ok);
-}
 
 extern "C" {
 
@@ -497,35 +405,32 @@ int toa_llc_read_probe(toa_handle h, const void* src_dev, size_t bytes, double* 
 int toa_robust_norm(toa_handle h, int kind, int dtype, int64_t count, const void* n2, double th2, void* loss, void* scale) {
   if (!h || !n2 || !loss || !scale || count < 0) return fail(TOA_E_ARG, "toa_robust_norm: null argument");
   if (kind < TOA_LOSS_L2 || kind > TOA_LOSS_BLAKE_ZISSERMAN) return fail(TOA_E_ARG, "toa_robust_norm: unknown loss kind");
-  if (dtype != TOA_F32 && dtype != TOA_F64) return fail(TOA_E_ARG, "toa_robust_norm: dtype must be TOA_F32 or TOA_F64");
+  if (int rc = check_dtype(dtype, "toa_robust_norm: ")) return rc;
   if (count == 0) return TOA_OK;
   TOA_ON_DEVICE(h->device);
   const unsigned grid = unsigned((count + 255) / 256);
-  if (dtype == TOA_F32)
-    hipLaunchKernelGGL(toa::robust_norm_kernel<float>, dim3(grid), dim3(256), 0, h->stream, kind, (long long)count,
-                       (const float*)n2, float(th2), (float*)loss, (float*)scale);
-  else
-    hipLaunchKernelGGL(toa::robust_norm_kernel<double>, dim3(grid), dim3(256), 0, h->stream, kind, (long long)count,
-                       (const double*)n2, th2, (double*)loss, (double*)scale);
-  HIP_TRY(hipGetLastError());
-  return TOA_OK;
+  return by_dtype(dtype, [&](auto tag) -> int {
+    using T = decltype(tag);
+    hipLaunchKernelGGL(toa::robust_norm_kernel<T>, dim3(grid), dim3(256), 0, h->stream, kind, (long long)count, (const T*)n2, T(th2),
+                       (T*)loss, (T*)scale);
+    HIP_TRY(hipGetLastError());
+    return TOA_OK;
+  });
 }
 
 int toa_jet_eval(toa_handle h, int fn, int dtype, int64_t count, const void* a, const void* b, void* out) {
   if (!h || !a || !b || !out || count < 0) return fail(TOA_E_ARG, "toa_jet_eval: null argument");
   if (fn < 0 || fn > 46) return fail(TOA_E_ARG, "toa_jet_eval: unknown function id");
-  if (dtype != TOA_F32 && dtype != TOA_F64) return fail(TOA_E_ARG, "dtype must be TOA_F32 or TOA_F64");
+  if (int rc = check_dtype(dtype)) return rc;
   if (count == 0) return TOA_OK;
   TOA_ON_DEVICE(h->device);
   const unsigned grid = unsigned((count + 255) / 256);
-  if (dtype == TOA_F32)
-    hipLaunchKernelGGL(toa::jet_eval_kernel<float>, dim3(grid), dim3(256), 0, h->stream, fn, (long long)count, (const float*)a,
-                       (const float*)b, (float*)out);
-  else
-    hipLaunchKernelGGL(toa::jet_eval_kernel<double>, dim3(grid), dim3(256), 0, h->stream, fn, (long long)count, (const double*)a,
-                       (const double*)b, (double*)out);
-  HIP_TRY(hipGetLastError());
-  return TOA_OK;
+  return by_dtype(dtype, [&](auto tag) -> int {
+    using T = decltype(tag);
+    hipLaunchKernelGGL(toa::jet_eval_kernel<T>, dim3(grid), dim3(256), 0, h->stream, fn, (long long)count, (const T*)a, (const T*)b, (T*)out);
+    HIP_TRY(hipGetLastError());
+    return TOA_OK;
+  });
 }
 
 int toa_abi_version(void) { return TOA_ABI_VERSION; }
@@ -612,7 +517,7 @@ static int check_model(int model, int n, int m, const void* data) {
 }
 
 static int check_shape(int dtype, int n, int m, int64_t P) {
-  if (dtype != TOA_F32 && dtype != TOA_F64) return fail(TOA_E_ARG, "dtype must be TOA_F32 or TOA_F64");
+  if (int rc = check_dtype(dtype)) return rc;
   if (n < 1 || n > 63) return fail(TOA_E_ARG, "n must be in [1, 63] on the LDS-resident path");
   if (m < 1) return fail(TOA_E_ARG, "m must be >= 1");
   if (P < 0 || P > 0x7fffffff) return fail(TOA_E_ARG, "P out of range");
@@ -639,14 +544,12 @@ int toa_dense_row_pack(toa_handle h, int dtype, int n, int m, int64_t P, const v
   TOA_ON_DEVICE(h->device);
   const DenseRowLayout L = DenseRowLayout::make(n, m);
   const int grid = h->num_cus * 8;
-  if (dtype == TOA_F32)
-    hipLaunchKernelGGL(dense_row_pack_kernel<float>, dim3(grid), dim3(256), 0, h->stream, (const float*)A, (const float*)b,
-                       (float*)packed, (long long)P, n, m, L);
-  else
-    hipLaunchKernelGGL(dense_row_pack_kernel<double>, dim3(grid), dim3(256), 0, h->stream, (const double*)A, (const double*)b,
-                       (double*)packed, (long long)P, n, m, L);
-  HIP_TRY(hipGetLastError());
-  return TOA_OK;
+  return by_dtype(dtype, [&](auto tag) -> int {
+    using T = decltype(tag);
+    hipLaunchKernelGGL(dense_row_pack_kernel<T>, dim3(grid), dim3(256), 0, h->stream, (const T*)A, (const T*)b, (T*)packed, (long long)P, n, m, L);
+    HIP_TRY(hipGetLastError());
+    return TOA_OK;
+  });
 }
 
 int toa_dense_row_synth(toa_handle h, int dtype, int n, int m, int64_t P, uint64_t seed, int64_t problem0,
@@ -658,22 +561,22 @@ int toa_dense_row_synth(toa_handle h, int dtype, int n, int m, int64_t P, uint64
   TOA_ON_DEVICE(h->device);
   const DenseRowLayout L = DenseRowLayout::make(n, m);
   const int grid = h->num_cus * 16;
-  if (dtype == TOA_F32)
-    hipLaunchKernelGGL(dense_row_synth_kernel<float>, dim3(grid), dim3(256), 0, h->stream, (float*)packed, (float*)x0,
-                       (float*)xstar, (long long)P, n, m, L, (unsigned long long)seed, (long long)problem0);
-  else
-    hipLaunchKernelGGL(dense_row_synth_kernel<double>, dim3(grid), dim3(256), 0, h->stream, (double*)packed, (double*)x0,
-                       (double*)xstar, (long long)P, n, m, L, (unsigned long long)seed, (long long)problem0);
-  HIP_TRY(hipGetLastError());
-  return TOA_OK;
+  return by_dtype(dtype, [&](auto tag) -> int {
+    using T = decltype(tag);
+    hipLaunchKernelGGL(dense_row_synth_kernel<T>, dim3(grid), dim3(256), 0, h->stream, (T*)packed, (T*)x0, (T*)xstar, (long long)P, n, m, L,
+                       (unsigned long long)seed, (long long)problem0);
+    HIP_TRY(hipGetLastError());
+    return TOA_OK;
+  });
 }
 
 static int check_loss_supported(toa_handle h, int model, const char* who);
 int toa_accumulate(toa_handle h, int model, int dtype, int n, int m, int64_t P, const void* data, const void* x,
                    int want_grad, void* g, void* H, double* cost, int32_t* nres) {
   if (!h) return fail(TOA_E_ARG, "null handle");
+  const AccumArgs a{n, m, P, data, x, want_grad, g, H, cost, nres};
   if (model == TOA_MODEL_DENSE_ROW_NATURAL) {  // the seam beyond one wavefront (SolverGN::Accumulate / Evaluate at any Dims, gn.h:97-113)
-    if (dtype != TOA_F32 && dtype != TOA_F64) return fail(TOA_E_ARG, "dtype must be TOA_F32 or TOA_F64");
+    if (int rc = check_dtype(dtype)) return rc;
     if (n < 1 || n > 4096) return fail(TOA_E_ARG, "TOA_MODEL_DENSE_ROW_NATURAL: n must be in [1, 4096]");
     if (m < 1 || P < 0 || !data) return fail(TOA_E_ARG, "toa_accumulate: bad shape or null data pointer");
     if (!x || !cost || (want_grad && (!g || !H))) return fail(TOA_E_ARG, "toa_accumulate: null pointer");
@@ -683,8 +586,8 @@ int toa_accumulate(toa_handle h, int model, int dtype, int n, int m, int64_t P, 
     // natural layout takes — n > 128 up to 4096, n < 64, toa_set_loss at any n — is ONE data pass of the launch-per-stage pipeline
     // (rows kernel + Gram, ours or the library's; round 6).
     if (h->loss == TOA_LOSS_L2 && toa_large_fused_eligible(h, dtype, n, m))
-      return toa_large_accumulate(h, dtype, n, m, P, data, x, want_grad, g, H, cost, nres);
-    return toa_large_accumulate_pipeline(h, dtype, n, m, P, data, x, want_grad, g, H, cost, nres);
+      return toa_large_accumulate(h, dtype, a);
+    return toa_large_accumulate_pipeline(h, dtype, a);
   }
   if (int rc = check_shape(dtype, n, m, P)) return rc;
   if (int rc = check_model(model, n, m, data)) return rc;
@@ -692,17 +595,14 @@ int toa_accumulate(toa_handle h, int model, int dtype, int n, int m, int64_t P, 
   if (!x || !cost || (want_grad && (!g || !H))) return fail(TOA_E_ARG, "toa_accumulate: null pointer");
   if (P == 0) return TOA_OK;
   TOA_ON_DEVICE(h->device);
-  const int dtag = dtype == TOA_F32 ? 0 : 1;
-  if (model == TOA_MODEL_DENSE_ROW_AD)
-    return dtag == 0 ? toa_inst_jetrow_accumulate_0_0(h, n, m, P, data, x, want_grad, g, H, cost, nres)
-                     : toa_inst_jetrow_accumulate_1_0(h, n, m, P, data, x, want_grad, g, H, cost, nres);
-  if (model != TOA_MODEL_DENSE_ROW)
-    return toa_inst_misc_accumulate(dtag, model, 16 * ((n + 15) / 16), h, n, m, P, data, x, want_grad, g, H, cost, nres);
-  const DenseRowLayout lay_ = DenseRowLayout::make(n, m);
-  if (h->loss == TOA_LOSS_L2 && !h->tune.narrow_mfma_pass && dense_row_lane_route(dtag, n, false))
-    return dtag == 0 ? toa_inst_narrow_accumulate_0_0(h, n, m, P, data, x, want_grad, g, H, cost, nres)
-                     : toa_inst_narrow_accumulate_1_0(h, n, m, P, data, x, want_grad, g, H, cost, nres);
-  return toa_inst_accumulate(dtag, lay_.nbm, lay_.thin, h, n, m, P, data, x, want_grad, g, H, cost, nres);
+  const toa_inst_table& inst = kInst[dtag_of(dtype)];
+  const DenseRowLayout lay = DenseRowLayout::make(n, m);
+  switch (small_accumulate_route(model, dtag_of(dtype), n, h->loss != TOA_LOSS_L2, h->tune.narrow_mfma_pass != 0)) {
+    case SmallFamily::JetRowAccumulate: return inst.jetrow_accumulate(h, a);
+    case SmallFamily::MiscAccumulate: return inst.misc_accumulate(model, h, a);
+    case SmallFamily::NarrowAccumulate: return inst.narrow_accumulate(h, a);
+    default: return inst.dense[lay.nbm - 1].accumulate(lay.thin, h, a);
+  }
 }
 
 int toa_solve_damped(toa_handle h, int dtype, int n, int64_t P, const void* H, const void* g, double scale, void* dx,
@@ -713,7 +613,7 @@ int toa_solve_damped(toa_handle h, int dtype, int n, int64_t P, const void* H, c
   const bool force_lib = h->tune.large_library_solver != 0;
   const bool large = n > 63 || force_lib;
   if (large) {
-    if (dtype != TOA_F32 && dtype != TOA_F64) return fail(TOA_E_ARG, "dtype must be TOA_F32 or TOA_F64");
+    if (int rc = check_dtype(dtype)) return rc;
     if (n < 1 || n > 4096) return fail(TOA_E_ARG, "toa_solve_damped: n must be in [1, 4096]");
     if (P < 0 || P > 65535) return fail(TOA_E_ARG, "toa_solve_damped: P must be in [0, 65535] on the library path");
   } else if (int rc = check_shape(dtype, n, 1, P)) {
@@ -723,13 +623,13 @@ int toa_solve_damped(toa_handle h, int dtype, int n, int64_t P, const void* H, c
   if (P == 0) return TOA_OK;
   TOA_ON_DEVICE(h->device);
   if (large) return toa_large_solve(h, dtype, n, P, H, g, scale, dx, ok);
-  return toa_inst_solve(dtype == TOA_F32 ? 0 : 1, 16 * ((n + 15) / 16), h, n, P, H, g, scale, dx, ok);
+  return kInst[dtag_of(dtype)].solve(npad_of(n), h, n, P, H, g, scale, dx, ok);
 }
 
 int toa_inv_cov(toa_handle h, int dtype, int n, int64_t P, const void* H, void* C, int32_t* ok) {
   if (!h) return fail(TOA_E_ARG, "null handle");
   if (n > 63) {  // beyond one wavefront: Cholesky against the identity through rocSOLVER (large_n.hip)
-    if (dtype != TOA_F32 && dtype != TOA_F64) return fail(TOA_E_ARG, "dtype must be TOA_F32 or TOA_F64");
+    if (int rc = check_dtype(dtype)) return rc;
     if (n > 4096) return fail(TOA_E_ARG, "toa_inv_cov: n must be in [1, 4096]");
     if (P < 0 || P > 65535) return fail(TOA_E_ARG, "toa_inv_cov: P must be in [0, 65535] for n > 63");
     if (!H || !C || !ok) return fail(TOA_E_ARG, "toa_inv_cov: null pointer");
@@ -741,7 +641,7 @@ int toa_inv_cov(toa_handle h, int dtype, int n, int64_t P, const void* H, void* 
   if (!H || !C || !ok) return fail(TOA_E_ARG, "toa_inv_cov: null pointer");
   if (P == 0) return TOA_OK;
   TOA_ON_DEVICE(h->device);
-  return toa_inst_inv_cov(dtype == TOA_F32 ? 0 : 1, 16 * ((n + 15) / 16), h, n, P, H, C, ok);
+  return kInst[dtag_of(dtype)].inv_cov(npad_of(n), h, n, P, H, C, ok);
 }
 
 // toa_set_loss is sticky handle state: a launch of a family that has no M-estimator while a loss is set would silently be a
@@ -758,13 +658,35 @@ static int check_loss_supported(toa_handle h, int model, const char* who) {
   }
 }
 
+// the fused kernel's parameter block as the C entry points fill it (the launchers of host_launch.hpp add what they decide)
+static FusedParams fused_params(toa_handle h, int n, int m, int64_t P, const void* data, void* x, const toa_options* options, const toa_results* results,
+                                uint64_t* counters, int mode, void* state, int32_t* active, const int32_t* stop_request) {
+  FusedParams prm;
+  std::memset(&prm, 0, sizeof(prm));
+  prm.data = data;
+  prm.x = x;
+  prm.P = P;
+  prm.n = n;
+  prm.m = m;
+  prm.opt = *options;
+  prm.res = *results;
+  prm.counters = reinterpret_cast<unsigned long long*>(counters);
+  prm.mode = mode;
+  prm.state = state;
+  prm.active = active;
+  prm.stop_request = stop_request;
+  prm.loss = h->loss;
+  prm.loss_th2 = h->loss_th2;
+  return prm;
+}
+
 static int lm_run_impl(toa_handle h, int model, int dtype, int n, int m, int64_t P, const void* data, void* x,
                        const toa_options* options, const toa_results* results, uint64_t* counters, int splits,
                        int mode = 0, void* state = nullptr, int32_t* active = nullptr, const int32_t* stop_request = nullptr) {
   if (!h) return fail(TOA_E_ARG, "null handle");
   const bool natural = model == TOA_MODEL_DENSE_ROW_NATURAL;  // n beyond one wavefront (large_fused.hip / large_n.hip)
   if (natural) {
-    if (dtype != TOA_F32 && dtype != TOA_F64) return fail(TOA_E_ARG, "dtype must be TOA_F32 or TOA_F64");
+    if (int rc = check_dtype(dtype)) return rc;
     // (beyond 1024 unknowns every stage of a pass is the library's — rocBLAS GEMM / GEMV, rocSOLVER potrf / potrs or LU — like
     //  toa_solve_damped, which takes n up to 4096 the same way; the reference's Dims == Dynamic is unbounded, optimizer.h:61-92)
     if (n < 1 || n > 4096) return fail(TOA_E_ARG, "TOA_MODEL_DENSE_ROW_NATURAL: n must be in [1, 4096]");
@@ -782,74 +704,32 @@ static int lm_run_impl(toa_handle h, int model, int dtype, int n, int m, int64_t
   if (int rc = check_run_args("toa_lm_run", options, results, 0, 1, "0 (LM) or 1 (GN) on this path")) return rc;  // optimize.h:75
   if (P == 0) return TOA_OK;
   TOA_ON_DEVICE(h->device);
+  if (mode != 0 && !state) return fail(TOA_E_ARG, "toa_lm_begin / toa_lm_step: state_dev is null");
   if (natural) {
     // (toa_set_loss: every form of this family applies it since round 5 — the one-kernel form at 64 <= n <= 128, the
     //  launch-per-stage pipeline beyond, for fp64 rows above n = 96, and under the stepping form)
-    if (mode != 0) {   // the stepping form runs on the launch-per-stage pipeline for every n >= 64 (large_n.hip)
-      if (!state) return fail(TOA_E_ARG, "toa_lm_begin / toa_lm_step: state_dev is null");
-      return toa_large_lm_step(h, dtype, n, m, P, data, x, options, results, counters, mode, state, active, stop_request);
-    }
+    // the stepping form runs on the launch-per-stage pipeline for every n >= 64 (large_n.hip)
+    if (mode != 0) return toa_large_lm_step(h, dtype, n, m, P, data, x, options, results, counters, mode, state, active, stop_request);
     return toa_large_lm_run(h, dtype, n, m, P, data, x, options, results, counters);
   }
-  FusedParams prm;
-  std::memset(&prm, 0, sizeof(prm));
-  prm.data = data;
-  prm.x = x;
-  prm.P = P;
-  prm.n = n;
-  prm.m = m;
-  prm.opt = *options;
-  prm.res = *results;
-  prm.counters = reinterpret_cast<unsigned long long*>(counters);
-  prm.mode = mode;
-  prm.state = state;
-  prm.active = active;
-  prm.stop_request = stop_request;
-  prm.loss = h->loss;
-  prm.loss_th2 = h->loss_th2;
-  if (mode != 0) {
-    if (!state) return fail(TOA_E_ARG, "toa_lm_begin / toa_lm_step: state_dev is null");
-    // the stepping form runs on the launch-per-iteration kernels with one chunk per problem (launch_stepping)
-    const DenseRowLayout lay_s = DenseRowLayout::make(n, m);
-    if (model == TOA_MODEL_DENSE_ROW_AD) return dtype == TOA_F32 ? toa_inst_jetrow_wide_0_0(n, h, prm) : toa_inst_jetrow_wide_1_0(n, h, prm);
-    return toa_inst_wide(dtype == TOA_F32 ? 0 : 1, model, lay_s.nbm, lay_s.thin, h, prm, 1);
+  const FusedParams prm = fused_params(h, n, m, P, data, x, options, results, counters, mode, state, active, stop_request);
+  // who runs it: small_route.hpp; the instance keys of inst.hpp
+  const int dtag = dtag_of(dtype);
+  const toa_inst_table& inst = kInst[dtag];
+  const DenseRowLayout lay = DenseRowLayout::make(n, m);
+  const SmallRoute route = small_lm_route(model, dtag, n, m, P, h->num_cus, splits, mode, h->loss != TOA_LOSS_L2, h->tune.narrow_mfma_pass != 0,
+                                          h->tune.wide_no_autosplit != 0, h->tune.wide_team_max_per_cu);
+  switch (route.family) {
+    case SmallFamily::JetRowStepping: return inst.jetrow_wide(n, h, prm);
+    case SmallFamily::Wide:
+      if (model != TOA_MODEL_DENSE_ROW) return inst.misc_wide(model, h, prm, route.splits);
+      return inst.dense[lay.nbm - 1].wide(lay.thin, h, prm, route.splits);
+    case SmallFamily::NarrowFused: return inst.narrow_fused(n, h, prm);
+    case SmallFamily::JetRowFused: return inst.jetrow_fused(n, h, prm);
+    case SmallFamily::MiscFused: return inst.misc_fused(model, npad_of(n), h, prm);
+    case SmallFamily::DenseFused: return inst.dense[lay.nbm - 1].fused(lay.thin, h, prm);
+    default: return fail(route.code, route.why);   // SmallFamily::Refused (the accumulate families are not small_lm_route's)
   }
-  const int dtag = dtype == TOA_F32 ? 0 : 1;
-  const DenseRowLayout lay_ = DenseRowLayout::make(n, m);
-  const bool splittable = model == TOA_MODEL_DENSE_ROW || model == TOA_MODEL_SE3_REPROJ;
-  // splits < 0: automatic — row-split when one-wave-per-problem would leave most of the chip idle
-  // (fewer problems than CUs and enough rows to give every chunk >= 256 of them)
-  //   or, for small problems (n <= 15, 512..4096 rows), the team form: one workgroup per problem has no co-residency
-  //   requirement, so it also pays for whole batches of them — measured (tests/tools/team_probe.py, C2-sized problems):
-  //   89-100 us for 1..256 problems against 131-144 us with one wavefront per problem; the crossover is one problem per
-  //   compute unit at n = 6 x 1000 rows and two at n = 12 x 2000.  toa_tuning::wide_team_max_per_cu overrides, toa_tuning::wide_no_autosplit disables.
-  if (splits == -1) {
-    const bool no_auto = h->tune.wide_no_autosplit != 0;
-    const long long team_env = h->tune.wide_team_max_per_cu;
-    const long long team_per_cu = team_env > 0 ? team_env : ((long long)m * (n + 1) >= 20000 ? 2 : 1);
-    const bool few = P * 4 <= h->num_cus && m >= 512;
-    const bool team = n <= 15 && m >= 512 && m <= 4096 && P <= team_per_cu * h->num_cus;
-    splits = (splittable && !no_auto && (few || team)) ? 0 : -1;
-  }
-  // DenseRow with an M-estimator on the handle: the robust data pass lives in the launch-per-iteration form (kernels.hpp
-  // RobustOf): chunked automatically for a few huge problems, one chunk per problem for a batch
-  // (round 6: where a row-per-lane instance exists — inst.hip — a BATCH runs the loss inside the fused kernel instead)
-  if (model == TOA_MODEL_DENSE_ROW && h->loss != TOA_LOSS_L2 && splits < 0) {
-    const bool few = P * 4 <= h->num_cus && m >= 512;
-    if (!few && !h->tune.narrow_mfma_pass && dense_row_lane_route(dtag, n, true))
-      return dtag == 0 ? toa_inst_narrow_fused_0_0(n, h, prm) : toa_inst_narrow_fused_1_0(n, h, prm);
-    splits = few ? 0 : 1;
-  }
-  if (splits >= 0) {
-    if (!splittable) return fail(TOA_E_UNSUPPORTED, "row-split execution is available for DenseRow and SE3Reproj");
-    return toa_inst_wide(dtag, model, lay_.nbm, lay_.thin, h, prm, splits);
-  }
-  if (model == TOA_MODEL_DENSE_ROW_AD) return dtag == 0 ? toa_inst_jetrow_fused_0_0(n, h, prm) : toa_inst_jetrow_fused_1_0(n, h, prm);
-  if (model != TOA_MODEL_DENSE_ROW) return toa_inst_misc_fused(dtag, model, 16 * ((n + 15) / 16), h, prm);
-  // narrow fp32 blocks: a row per lane (RowModel) instead of sixteen lanes per row (toa_tuning::narrow_mfma_pass: the old route)
-  if (!h->tune.narrow_mfma_pass && dense_row_lane_route(dtag, n, false)) return dtag == 0 ? toa_inst_narrow_fused_0_0(n, h, prm) : toa_inst_narrow_fused_1_0(n, h, prm);
-  return toa_inst_fused(dtag, lay_.nbm, lay_.thin, h, prm);
-  return fail(TOA_E_ARG, "toa_lm_run: bad block count");
 }
 
 // The system (Hessians, work matrices) cannot be allocated: the reference does not throw — ResizeIfNeeded catches
@@ -898,7 +778,7 @@ int toa_lm_step_info(toa_handle h, int dtype, int n, int64_t P, const void* stat
                      double* grad_norm2_dev, void* dx_dev, void* g_dev) {
   if (!h || !state_dev) return fail(TOA_E_ARG, "toa_lm_step_info: null argument");
   if (n >= 64) {
-    if ((dtype != TOA_F32 && dtype != TOA_F64) || n > 4096 || P < 0 || P > 65535) return fail(TOA_E_ARG, "toa_lm_step_info: bad shape");
+    if (!dtype_ok(dtype) || n > 4096 || P < 0 || P > 65535) return fail(TOA_E_ARG, "toa_lm_step_info: bad shape");
     if (P == 0) return TOA_OK;
     TOA_ON_DEVICE(h->device);
     return toa_large_step_info(h, dtype, n, P, state_dev, err_dev, dx_norm2_dev, grad_norm2_dev, dx_dev, g_dev);
@@ -907,21 +787,20 @@ int toa_lm_step_info(toa_handle h, int dtype, int n, int64_t P, const void* stat
   if (P == 0) return TOA_OK;
   TOA_ON_DEVICE(h->device);
   const unsigned grid = unsigned((P + 3) / 4);
-  if (dtype == TOA_F32)
-    hipLaunchKernelGGL(toa::step_info_kernel<float>, dim3(grid), dim3(256), 0, h->stream, state_dev, (long long)P, n, err_dev,
-                       dx_norm2_dev, grad_norm2_dev, (float*)dx_dev, (float*)g_dev);
-  else
-    hipLaunchKernelGGL(toa::step_info_kernel<double>, dim3(grid), dim3(256), 0, h->stream, state_dev, (long long)P, n, err_dev,
-                       dx_norm2_dev, grad_norm2_dev, (double*)dx_dev, (double*)g_dev);
-  HIP_TRY(hipGetLastError());
-  return TOA_OK;
+  return by_dtype(dtype, [&](auto tag) -> int {
+    using T = decltype(tag);
+    hipLaunchKernelGGL(toa::step_info_kernel<T>, dim3(grid), dim3(256), 0, h->stream, state_dev, (long long)P, n, err_dev, dx_norm2_dev,
+                       grad_norm2_dev, (T*)dx_dev, (T*)g_dev);
+    HIP_TRY(hipGetLastError());
+    return TOA_OK;
+  });
 }
 
 int toa_lm_step_log(toa_handle h, int dtype, int n, int64_t P, const void* state_dev, double* lambda_dev, int32_t* num_residuals_dev,
                     int32_t* num_inliers_dev) {
   if (!h || !state_dev) return fail(TOA_E_ARG, "toa_lm_step_log: null argument");
   if (n >= 64) {
-    if ((dtype != TOA_F32 && dtype != TOA_F64) || n > 4096 || P < 0 || P > 65535) return fail(TOA_E_ARG, "toa_lm_step_log: bad shape");
+    if (!dtype_ok(dtype) || n > 4096 || P < 0 || P > 65535) return fail(TOA_E_ARG, "toa_lm_step_log: bad shape");
     if (P == 0) return TOA_OK;
     TOA_ON_DEVICE(h->device);
     return toa_large_step_log(h, dtype, n, P, state_dev, lambda_dev, num_residuals_dev, num_inliers_dev);
@@ -930,12 +809,12 @@ int toa_lm_step_log(toa_handle h, int dtype, int n, int64_t P, const void* state
   if (P == 0) return TOA_OK;
   TOA_ON_DEVICE(h->device);
   const unsigned grid = unsigned((P + 255) / 256);
-  if (dtype == TOA_F32)
-    hipLaunchKernelGGL(toa::step_log_kernel<float>, dim3(grid), dim3(256), 0, h->stream, state_dev, (long long)P, lambda_dev, num_residuals_dev, num_inliers_dev);
-  else
-    hipLaunchKernelGGL(toa::step_log_kernel<double>, dim3(grid), dim3(256), 0, h->stream, state_dev, (long long)P, lambda_dev, num_residuals_dev, num_inliers_dev);
-  HIP_TRY(hipGetLastError());
-  return TOA_OK;
+  return by_dtype(dtype, [&](auto tag) -> int {
+    using T = decltype(tag);
+    hipLaunchKernelGGL(toa::step_log_kernel<T>, dim3(grid), dim3(256), 0, h->stream, state_dev, (long long)P, lambda_dev, num_residuals_dev, num_inliers_dev);
+    HIP_TRY(hipGetLastError());
+    return TOA_OK;
+  });
 }
 
 int toa_lm_run_split(toa_handle h, int model, int dtype, int n, int m, int64_t P, const void* data, void* x,

@@ -86,10 +86,26 @@ bool toa_large_fused_eligible(toa_context* h, int dtype, int n, int m);
 int toa_large_fused_lm_run(toa_context* h, int dtype, int n, int m, int64_t P, const void* data, void* x, const toa_options* options,
                            const toa_results* results, uint64_t* counters);
 
-int toa_large_accumulate(toa_context* h, int dtype, int n, int m, int64_t P, const void* data, const void* x, int want_grad, void* g,
-                         void* H, double* cost, int32_t* nres);
-int toa_large_accumulate_pipeline(toa_context* h, int dtype, int n, int m, int64_t P, const void* data, const void* x, int want_grad, void* g,
-                                  void* H, double* cost, int32_t* nres);
+// What one data pass at a given x is asked for (toa_accumulate, include/tinyopt_amd.h): the shape, the inputs, and where g, H (with
+// want_grad), the cost and the residual count go.  Device pointers, typed by the dtype / the model of whoever takes it.
+namespace toa {
+struct AccumArgs {
+  int n, m;
+  int64_t P;
+  const void* data;
+  const void* x;
+  int want_grad;
+  void* g;
+  void* H;
+  double* cost;
+  int32_t* nres;
+};
+// the f32 / f64 fan-out of the C entry points: f(float()) or f(double())
+template <typename F>
+int by_dtype(int dtype, F&& f) { return dtype == TOA_F32 ? f(float()) : f(double()); }
+}  // namespace toa
+int toa_large_accumulate(toa_context* h, int dtype, const toa::AccumArgs& a);
+int toa_large_accumulate_pipeline(toa_context* h, int dtype, const toa::AccumArgs& a);
 
 // error reporting lives in capi.hip (one thread_local message for the whole library)
 int toa_fail(int code, const std::string& msg);
@@ -287,21 +303,20 @@ inline void coop_chunking(toa_handle h, int n, int m, int* K_out, int* cs_out) {
   *K_out = (steps_total + cs - 1) / cs;
 }
 template <typename Model>
-inline int launch_accumulate(toa_handle h, int n, int m, int64_t P, const void* data, const void* x, int want_grad,
-                             void* g, void* H, double* cost, int32_t* nres) {
+inline int launch_accumulate(toa_handle h, const AccumArgs& a) {
   using T = typename Model::Scalar;
-  const long long grid = accumulate_grid(h, P);
+  const long long grid = accumulate_grid(h, a.P);
   size_t pw, pwg;
-  if (int rc = lds_fit<T>(h, n, &pw, &pwg, 4, ModelStageBytes<Model>::value)) return rc;
+  if (int rc = lds_fit<T>(h, a.n, &pw, &pwg, 4, ModelStageBytes<Model>::value)) return rc;
   using RModel = typename RobustOf<Model>::type;
   if (h->loss != TOA_LOSS_L2 && !std::is_same<RModel, Model>::value) {
     if (int rc = ensure_lds_attr(h, (const void*)accumulate_kernel<RModel>, pwg)) return rc;
-    hipLaunchKernelGGL((accumulate_kernel<RModel>), dim3((unsigned)grid), dim3(256), pwg, h->stream, data, x, (long long)P, n, m,
-                       want_grad, g, H, cost, nres, (int)pw, h->loss, h->loss_th2);
+    hipLaunchKernelGGL((accumulate_kernel<RModel>), dim3((unsigned)grid), dim3(256), pwg, h->stream, a.data, a.x, (long long)a.P, a.n, a.m,
+                       a.want_grad, a.g, a.H, a.cost, a.nres, (int)pw, h->loss, h->loss_th2);
   } else {
     if (int rc = ensure_lds_attr(h, (const void*)accumulate_kernel<Model>, pwg)) return rc;
-    hipLaunchKernelGGL((accumulate_kernel<Model>), dim3((unsigned)grid), dim3(256), pwg, h->stream, data, x, (long long)P, n, m,
-                       want_grad, g, H, cost, nres, (int)pw, h->loss, h->loss_th2);
+    hipLaunchKernelGGL((accumulate_kernel<Model>), dim3((unsigned)grid), dim3(256), pwg, h->stream, a.data, a.x, (long long)a.P, a.n, a.m,
+                       a.want_grad, a.g, a.H, a.cost, a.nres, (int)pw, h->loss, h->loss_th2);
   }
   HIP_TRY(hipGetLastError());
   return TOA_OK;
@@ -692,16 +707,3 @@ inline int launch_inv_cov(toa_handle h, int n, int64_t P, const void* H, void* C
   return TOA_OK;
 }
 }  // namespace toa
-
-// ---- per-(dtype, NBM) entry points defined in inst.hip (dtag: 0 = f32, 1 = f64) ----
-int toa_inst_fused(int dtag, int nbm, int thin, toa_handle h, const toa::FusedParams& prm);
-int toa_inst_accumulate(int dtag, int nbm, int thin, toa_handle h, int n, int m, int64_t P, const void* data,
-                        const void* x, int want_grad, void* g, void* H, double* cost, int32_t* nres);
-// Gaussian-prior / sqrt2 models (inst.hip -DTOA_INST_MISC)
-int toa_inst_misc_fused(int dtag, int model, int npad, toa_handle h, const toa::FusedParams& prm);
-int toa_inst_misc_accumulate(int dtag, int model, int npad, toa_handle h, int n, int m, int64_t P, const void* data,
-                             const void* x, int want_grad, void* g, void* H, double* cost, int32_t* nres);
-int toa_inst_wide(int dtag, int model, int nbm, int thin, toa_handle h, const toa::FusedParams& prm, int splits);
-int toa_inst_inv_cov(int dtag, int npad, toa_handle h, int n, int64_t P, const void* H, void* C, int32_t* ok);
-int toa_inst_solve(int dtag, int npad, toa_handle h, int n, int64_t P, const void* H, const void* g, double scale,
-                   void* dx, int32_t* ok);

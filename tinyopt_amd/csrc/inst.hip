@@ -1,6 +1,7 @@
 // One translation unit per (dtype, block count): compiled with -DTOA_INST_DT={0,1} -DTOA_INST_NBM={1..4},
 // or -DTOA_INST_SOLVE -DTOA_INST_DT={0,1} for the K3 seam kernels.  See __graft_entry__.build().
 #include "kernels.hpp"
+#include "inst.hpp"   // the list of what this file defines; C linkage, so a definition that differs from it does not compile
 using namespace toa;
 
 #if TOA_INST_DT == 0
@@ -11,6 +12,7 @@ using InstT = double;
 #define TOA_CAT2(a, b, c) a##b##_##c
 #define TOA_CAT(a, b, c) TOA_CAT2(a, b, c)
 
+extern "C" {
 #ifdef TOA_INST_MISC
 int TOA_CAT(toa_inst_misc_fused_, TOA_INST_DT, 0)(int model, int npad, toa_handle h, const FusedParams& prm) {
   if (model == TOA_MODEL_SQRT2) return launch_fused<Sqrt2Model<InstT>>(h, prm);
@@ -70,22 +72,15 @@ int TOA_CAT(toa_inst_misc_wide_, TOA_INST_DT, 0)(int model, toa_handle h, const 
     default: return launch_stepping<GaussianPriorModel<InstT, 64>, 64, E>(h, prm);
   }
 }
-int TOA_CAT(toa_inst_misc_accumulate_, TOA_INST_DT, 0)(int model, int npad, toa_handle h, int n, int m, int64_t P,
-                                                       const void* data, const void* x, int want_grad, void* g, void* H,
-                                                       double* cost, int32_t* nres) {
-  (void)npad;
-  if (model == TOA_MODEL_SQRT2) return launch_accumulate<Sqrt2Model<InstT>>(h, n, m, P, data, x, want_grad, g, H, cost, nres);
-  if (model == TOA_MODEL_TESTFN) return launch_accumulate<TestFnModel<InstT>>(h, n, m, P, data, x, want_grad, g, H, cost, nres);
-  if (model == TOA_MODEL_SE3_REPROJ)
-    return launch_accumulate<Se3ReprojModel<InstT>>(h, n, m, P, data, x, want_grad, g, H, cost, nres);
-  if (model == TOA_MODEL_SE3_PRIOR)
-    return launch_accumulate<Se3PriorModel<InstT>>(h, n, m, P, data, x, want_grad, g, H, cost, nres);
-  if (model == TOA_MODEL_CIRCLE_FIT)
-    return launch_accumulate<JetModel<InstT, CircleFitFunctor<InstT>>>(h, n, m, P, data, x, want_grad, g, H, cost, nres);
-  if (model == TOA_MODEL_DENSE_ROW_AD6)
-    return launch_accumulate<JetModel<InstT, DenseRowAdFunctor<InstT, 6>>>(h, n, m, P, data, x, want_grad, g, H, cost, nres);
-  if (model == TOA_MODEL_MAHA_PRIOR) return launch_accumulate<MahaPriorModel<InstT, 16>>(h, n, m, P, data, x, want_grad, g, H, cost, nres);
-  return launch_accumulate<GaussianPriorModel<InstT, 16>>(h, n, m, P, data, x, want_grad, g, H, cost, nres);
+int TOA_CAT(toa_inst_misc_accumulate_, TOA_INST_DT, 0)(int model, toa_handle h, const AccumArgs& a) {
+  if (model == TOA_MODEL_SQRT2) return launch_accumulate<Sqrt2Model<InstT>>(h, a);
+  if (model == TOA_MODEL_TESTFN) return launch_accumulate<TestFnModel<InstT>>(h, a);
+  if (model == TOA_MODEL_SE3_REPROJ) return launch_accumulate<Se3ReprojModel<InstT>>(h, a);
+  if (model == TOA_MODEL_SE3_PRIOR) return launch_accumulate<Se3PriorModel<InstT>>(h, a);
+  if (model == TOA_MODEL_CIRCLE_FIT) return launch_accumulate<JetModel<InstT, CircleFitFunctor<InstT>>>(h, a);
+  if (model == TOA_MODEL_DENSE_ROW_AD6) return launch_accumulate<JetModel<InstT, DenseRowAdFunctor<InstT, 6>>>(h, a);
+  if (model == TOA_MODEL_MAHA_PRIOR) return launch_accumulate<MahaPriorModel<InstT, 16>>(h, a);
+  return launch_accumulate<GaussianPriorModel<InstT, 16>>(h, a);
 }
 #elif defined(TOA_INST_JETROW)
 // TOA_MODEL_DENSE_ROW_AD: the DenseRow residual written as r(x) only, differentiated on the device for WIDE parameter
@@ -103,10 +98,10 @@ int TOA_CAT(toa_inst_jetrow_wide_, TOA_INST_DT, 0)(int n, toa_handle h, const Fu
   if (n == 50) return launch_stepping<RowModel<InstT, 3, 3, AdRowFunctor<InstT, DenseRowAdFunctor<InstT, 50>>>, 64, E>(h, prm);
   return toa_fail(TOA_E_UNSUPPORTED, "TOA_MODEL_DENSE_ROW_AD is instantiated for n = 12 and n = 50");
 }
-int TOA_CAT(toa_inst_jetrow_accumulate_, TOA_INST_DT, 0)(toa_handle h, int n, int m, int64_t P, const void* data, const void* x,
-                                                         int want_grad, void* g, void* H, double* cost, int32_t* nres) {
-  if (n == 12) return launch_accumulate<RowModel<InstT, 1, 0, AdRowFunctor<InstT, DenseRowAdFunctor<InstT, 12>>>>(h, n, m, P, data, x, want_grad, g, H, cost, nres);
-  if (n == 50) return launch_accumulate<RowModel<InstT, 3, 3, AdRowFunctor<InstT, DenseRowAdFunctor<InstT, 50>>>>(h, n, m, P, data, x, want_grad, g, H, cost, nres);
+int TOA_CAT(toa_inst_jetrow_accumulate_, TOA_INST_DT, 0)(toa_handle h, const AccumArgs& a) {
+  const int n = a.n;
+  if (n == 12) return launch_accumulate<RowModel<InstT, 1, 0, AdRowFunctor<InstT, DenseRowAdFunctor<InstT, 12>>>>(h, a);
+  if (n == 50) return launch_accumulate<RowModel<InstT, 3, 3, AdRowFunctor<InstT, DenseRowAdFunctor<InstT, 50>>>>(h, a);
   return toa_fail(TOA_E_UNSUPPORTED, "TOA_MODEL_DENSE_ROW_AD is instantiated for n = 12 and n = 50");
 }
 #elif defined(TOA_INST_NARROW)
@@ -136,7 +131,6 @@ int TOA_CAT(toa_inst_jetrow_accumulate_, TOA_INST_DT, 0)(toa_handle h, int n, in
 #endif
 // (two translation units per dtype — -DTOA_NARROW_PART=0: the JetModel fused kernels, 1: the RowModel ones, the seam and the dispatch — so that
 //  neither is the long pole of the build)
-int TOA_CAT(toa_inst_narrow_jet_fused_, TOA_INST_DT, 0)(int n, toa_handle h, const FusedParams& prm);
 #if TOA_NARROW_PART == 0
 int TOA_CAT(toa_inst_narrow_jet_fused_, TOA_INST_DT, 0)(int n, toa_handle h, const FusedParams& prm) {
   const bool robust = prm.loss != TOA_LOSS_L2;
@@ -165,12 +159,12 @@ int TOA_CAT(toa_inst_narrow_fused_, TOA_INST_DT, 0)(int n, toa_handle h, const F
 #undef TOA_NF
   return toa_fail(TOA_E_ARG, "DenseRow narrow route: no instance for this n");
 }
-int TOA_CAT(toa_inst_narrow_accumulate_, TOA_INST_DT, 0)(toa_handle h, int n, int m, int64_t P, const void* data, const void* x, int want_grad, void* g,
-                                                         void* H, double* cost, int32_t* nres) {
+int TOA_CAT(toa_inst_narrow_accumulate_, TOA_INST_DT, 0)(toa_handle h, const AccumArgs& a) {
+  const int n = a.n;
   const bool robust = false;   // (the seam takes this route for plain L2 only: capi.hip)
   (void)robust;
-#define TOA_NJ(N) return launch_accumulate<JetModel<InstT, DenseRowPackedFunctor<InstT, N>>>(h, n, m, P, data, x, want_grad, g, H, cost, nres)
-#define TOA_NA(NB, TH, N) return launch_accumulate<RowModel<InstT, NB, TH, DenseRowPackedFunctor<InstT, N>>>(h, n, m, P, data, x, want_grad, g, H, cost, nres)
+#define TOA_NJ(N) return launch_accumulate<JetModel<InstT, DenseRowPackedFunctor<InstT, N>>>(h, a)
+#define TOA_NA(NB, TH, N) return launch_accumulate<RowModel<InstT, NB, TH, DenseRowPackedFunctor<InstT, N>>>(h, a)
   TOA_NARROW_CASES(TOA_NJ, TOA_NA)
 #undef TOA_NJ
 #undef TOA_NA
@@ -233,18 +227,17 @@ int TOA_CAT(toa_inst_wide_, TOA_INST_DT, TOA_INST_NBM)(int thin, toa_handle h, c
     default: return toa_fail(TOA_E_ARG, "bad thin-tail width");
   }
 }
-int TOA_CAT(toa_inst_accumulate_, TOA_INST_DT, TOA_INST_NBM)(int thin, toa_handle h, int n, int m, int64_t P,
-                                                             const void* data, const void* x, int want_grad, void* g,
-                                                             void* H, double* cost, int32_t* nres) {
+int TOA_CAT(toa_inst_accumulate_, TOA_INST_DT, TOA_INST_NBM)(int thin, toa_handle h, const AccumArgs& a) {
   switch (thin) {
-    case 0: return launch_accumulate<DenseRowModel<InstT, TOA_INST_NBM, 0>>(h, n, m, P, data, x, want_grad, g, H, cost, nres);
+    case 0: return launch_accumulate<DenseRowModel<InstT, TOA_INST_NBM, 0>>(h, a);
 #if TOA_INST_NBM <= 3
-    case 1: return launch_accumulate<DenseRowModel<InstT, TOA_INST_NBM, 1>>(h, n, m, P, data, x, want_grad, g, H, cost, nres);
-    case 2: return launch_accumulate<DenseRowModel<InstT, TOA_INST_NBM, 2>>(h, n, m, P, data, x, want_grad, g, H, cost, nres);
-    case 3: return launch_accumulate<DenseRowModel<InstT, TOA_INST_NBM, 3>>(h, n, m, P, data, x, want_grad, g, H, cost, nres);
-    case 4: return launch_accumulate<DenseRowModel<InstT, TOA_INST_NBM, 4>>(h, n, m, P, data, x, want_grad, g, H, cost, nres);
+    case 1: return launch_accumulate<DenseRowModel<InstT, TOA_INST_NBM, 1>>(h, a);
+    case 2: return launch_accumulate<DenseRowModel<InstT, TOA_INST_NBM, 2>>(h, a);
+    case 3: return launch_accumulate<DenseRowModel<InstT, TOA_INST_NBM, 3>>(h, a);
+    case 4: return launch_accumulate<DenseRowModel<InstT, TOA_INST_NBM, 4>>(h, a);
 #endif
     default: return toa_fail(TOA_E_ARG, "bad thin-tail width");
   }
 }
 #endif
+}  // extern "C"

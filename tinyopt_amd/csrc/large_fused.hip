@@ -887,11 +887,10 @@ int toa_large_fused_lm_run(toa_handle h, int dtype, int n, int m, int64_t P, con
   return toa::large_fused_dispatch<double>(h, n, m, P, static_cast<const double*>(data), static_cast<double*>(x), *options, *results, counters);
 }
 
-int toa_large_accumulate(toa_handle h, int dtype, int n, int m, int64_t P, const void* data, const void* x, int want_grad, void* g,
-                         void* H, double* cost, int32_t* nres) {
+int toa_large_accumulate(toa_handle h, int dtype, const toa::AccumArgs& a) {
   if (dtype == TOA_F32)
-    return toa::large_accumulate_dispatch<float>(h, n, m, P, static_cast<const float*>(data), static_cast<const float*>(x), want_grad,
-                                                 static_cast<float*>(g), static_cast<float*>(H), cost, nres);
-  return toa::large_accumulate_dispatch<double>(h, n, m, P, static_cast<const double*>(data), static_cast<const double*>(x), want_grad,
-                                                static_cast<double*>(g), static_cast<double*>(H), cost, nres);
+    return toa::large_accumulate_dispatch<float>(h, a.n, a.m, a.P, static_cast<const float*>(a.data), static_cast<const float*>(a.x), a.want_grad,
+                                                 static_cast<float*>(a.g), static_cast<float*>(a.H), a.cost, a.nres);
+  return toa::large_accumulate_dispatch<double>(h, a.n, a.m, a.P, static_cast<const double*>(a.data), static_cast<const double*>(a.x), a.want_grad,
+                                                static_cast<double*>(a.g), static_cast<double*>(a.H), a.cost, a.nres);
 }

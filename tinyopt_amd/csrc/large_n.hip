@@ -2448,10 +2448,6 @@ int large_solve_own_t(toa_handle h, const LargeRouteChoice& route, int n, int64_
   return s.finish(dx, ok, a.active);
 }
 
-// the f32 / f64 fan-out of the C entry points: f(float()) or f(double())
-template <typename F>
-int by_dtype(int dtype, F&& f) { return dtype == TOA_F32 ? f(float()) : f(double()); }
-
 // The pipeline's kernels index problems through grid.y (65 535): a larger batch goes through it slice by slice — the
 // problems are independent, so the slices are just shorter batches (same bits), and the workspace is sized for one slice.
 // f(first problem, problems); run_empty: an empty batch still makes its one (empty) call.
@@ -2579,18 +2575,18 @@ int toa_large_lm_step(toa_handle h, int dtype, int n, int m, int64_t P, const vo
 
 // toa_accumulate for the natural layout where the one-launch kernel of large_fused.hip does not reach: n > 128, or an M-estimator
 // (one data pass of the pipeline; batches beyond grid.y = 65 535 problems slice by slice like toa_large_lm_run)
-int toa_large_accumulate_pipeline(toa_handle h, int dtype, int n, int m, int64_t P, const void* data, const void* x, int want_grad, void* g,
-                                  void* H, double* cost, int32_t* nres) {
+int toa_large_accumulate_pipeline(toa_handle h, int dtype, const toa::AccumArgs& a) {
   toa_options opt;
   toa_options_default(&opt);
   toa_results res{};
-  return toa::by_slices(P, false, [&](int64_t p0, int64_t Ps) -> int {
+  const size_t n = size_t(a.n), m = size_t(a.m);
+  return toa::by_slices(a.P, false, [&](int64_t p0, int64_t Ps) -> int {
     return toa::by_dtype(dtype, [&](auto tag) -> int {
       using T = decltype(tag);
-      const toa::LargeSeamOut<T> o{g ? static_cast<T*>(g) + size_t(p0) * size_t(n) : nullptr, H ? static_cast<T*>(H) + size_t(p0) * size_t(n) * size_t(n) : nullptr,
-                                   cost + p0, nres ? nres + p0 : nullptr, want_grad};
-      return toa::large_lm_run_t<T>(h, n, m, Ps, static_cast<const T*>(data) + size_t(p0) * size_t(m) * (size_t(n) + 1),
-                                    const_cast<T*>(static_cast<const T*>(x)) + size_t(p0) * size_t(n), opt, res, nullptr, toa::LargeMode::Accumulate,
+      const toa::LargeSeamOut<T> o{a.g ? static_cast<T*>(a.g) + size_t(p0) * n : nullptr, a.H ? static_cast<T*>(a.H) + size_t(p0) * n * n : nullptr,
+                                   a.cost + p0, a.nres ? a.nres + p0 : nullptr, a.want_grad};
+      return toa::large_lm_run_t<T>(h, a.n, a.m, Ps, static_cast<const T*>(a.data) + size_t(p0) * m * (n + 1),
+                                    const_cast<T*>(static_cast<const T*>(a.x)) + size_t(p0) * n, opt, res, nullptr, toa::LargeMode::Accumulate,
                                     nullptr, nullptr, nullptr, &o);
     });
   });

@@ -583,6 +583,21 @@ int toa_jit_accumulate(toa_handle h, toa_jit_model model, int num_items, int64_t
  *      Numeric bodies (toa_jit_spec::diff, and every twin) are compiled without floating-point contraction. */
 int toa_jit_check_gradient(toa_handle h, toa_jit_model model, int num_items, int64_t P, const void* data_dev, const void* x_dev,
                            double eps, int method, int check_H, double* max_dist_dev, int32_t* ok_dev);
+/*      diff::Eval / diff::CalculateJac (diff/auto_diff.h:14-138) for a run-time model at x_dev [P][xdim]: the residuals and the
+ *      Jacobian ROWS of every problem, written out instead of reduced —
+ *        res_dev [P][m]      m = num_items * residuals_per_item; an item's residuals are consecutive (toa_jit_accumulate's row order)
+ *        J_dev   [P][m][n]   row-major, n = num_params; on TOA_MANIFOLD_SE3 / TOA_MANIFOLD_USER over the TANGENT at d = 0
+ *                            (auto_diff.h:31-39), as the Accumulate seam forms it
+ *      in the model's scalar type.  At least one of the two is non-NULL: J_dev == NULL runs the body on plain scalars (no Jets, no
+ *      differences), res_dev == NULL is CalculateJac.  Served: TOA_JIT_RESIDUAL (Jets), TOA_JIT_ACCUMULATE (the body's own
+ *      Jacobian) and both with diff = TOA_DIFF_NUM_* (NumEval / EstimateNumJac, diff/num_diff.h:56-126).  Refused: scalar cost
+ *      kinds (TOA_E_ARG: toa_jit_accumulate already is Eval of a scalar function), a handle with a loss set (TOA_E_ARG: Eval is
+ *      the plain function), one problem whose items or whose J exceed 4 GiB (TOA_E_UNSUPPORTED).  P == 0 returns TOA_OK.
+ *      Stream-ordered, no handle workspace.  The kernels are a third code object of the model, built on the first call (then
+ *      cached on disk): that first call is refused with TOA_E_UNSUPPORTED under stream capture — run it once before
+ *      hipStreamBeginCapture. */
+int toa_jit_eval(toa_handle h, toa_jit_model model, int num_items, int64_t P, const void* data_dev, const void* x_dev, void* res_dev,
+                 void* J_dev);
 /*      Gradient descent (ABI 7): Optimize(x, cost, options) with options.solver_type = GradientDescent on a scalar cost model —
  *      gd::Optimizer = Optimizer_<SolverGD> (optimizers/gd.h; optimizer.h:242-539): every Step builds g = sum_i grad c_i (clamped by
  *      grad_clipping), dx = -lr * g, and judges, rolls back and stops exactly as the LM path does; no final Hessian is written

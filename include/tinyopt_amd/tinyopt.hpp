@@ -562,6 +562,48 @@ GradientCheck CheckGradient(const JitModel<Scalar>& model, const std::vector<Sca
   for (size_t p = 0; p < size_t(P); ++p) { out.max_dist_g[p] = d[2 * p]; out.max_dist_H[p] = d[2 * p + 1]; }
   return out;
 }
+
+// diff::Eval / diff::CalculateJac (diff/auto_diff.h:14-138) for a bound run-time residual model at x [P][xdim]: the residuals
+// [P][m] and the Jacobian rows [P][m][n], row-major, m = items x residuals_per_item in the row order of the Accumulate seam; on a
+// manifold J is over the tangent.  A numeric model (JitResidual's diff argument) gives NumEval / EstimateNumJac.  Not for scalar
+// cost models and not with a loss set (the library refuses both).
+template <typename Scalar>
+std::pair<std::vector<Scalar>, std::vector<Scalar>> Eval(const JitModel<Scalar>& model, const std::vector<Scalar>& x, bool jac = true) {
+  const int64_t P = model.P();
+  if (int64_t(x.size()) != P * model.xdim())
+    throw std::invalid_argument("tinyopt_amd::diff::Eval: x must hold P * (parameters per problem) scalars");
+  const Context& ctx = model.ctx();
+  const size_t rows = size_t(P) * size_t(model.m());
+  DeviceBuffer<Scalar> dx(ctx, x.size());
+  dx.upload(x.data());
+  DeviceBuffer<Scalar> res(ctx, rows);
+  DeviceBuffer<Scalar> J(ctx, jac ? rows * size_t(model.n()) : size_t(1));
+  apply_loss(model);
+  check(toa_jit_eval(ctx.get(), model.jit_handle(), model.items(), P, model.data(), dx.data(), res.data(), jac ? J.data() : nullptr));
+  check(toa_synchronize(ctx.get()));
+  std::pair<std::vector<Scalar>, std::vector<Scalar>> out;
+  out.first.resize(rows);
+  res.download(out.first.data());
+  if (jac) { out.second.resize(rows * size_t(model.n())); J.download(out.second.data()); }
+  return out;
+}
+template <typename Scalar>
+std::vector<Scalar> CalculateJac(const JitModel<Scalar>& model, const std::vector<Scalar>& x) {
+  const int64_t P = model.P();
+  if (int64_t(x.size()) != P * model.xdim())
+    throw std::invalid_argument("tinyopt_amd::diff::CalculateJac: x must hold P * (parameters per problem) scalars");
+  const Context& ctx = model.ctx();
+  const size_t elems = size_t(P) * size_t(model.m()) * size_t(model.n());
+  DeviceBuffer<Scalar> dx(ctx, x.size());
+  dx.upload(x.data());
+  DeviceBuffer<Scalar> J(ctx, elems);
+  apply_loss(model);
+  check(toa_jit_eval(ctx.get(), model.jit_handle(), model.items(), P, model.data(), dx.data(), nullptr, J.data()));
+  check(toa_synchronize(ctx.get()));
+  std::vector<Scalar> out(elems);
+  J.download(out.data());
+  return out;
+}
 }  // namespace diff
 
 // The reference's class / stepping form (`lm::Optimizer<H_t> optimizer(options)`; `optimizer.Step(x, acc, out)` one loop

@@ -1211,6 +1211,49 @@ def CheckGradient(model: "JitModel", x: torch.Tensor, eps: Optional[float] = Non
     return GradientCheck(ok != 0, dist[:, 0], dist[:, 1], e)
 
 
+def _eval_out(t: Optional[torch.Tensor], shape, x: torch.Tensor, what: str) -> torch.Tensor:
+    if t is None:
+        return torch.empty(shape, dtype=x.dtype, device=x.device)
+    if tuple(t.shape) != tuple(shape) or t.dtype != x.dtype or t.device != x.device or not t.is_contiguous():
+        raise ValueError(f"{what} must be a contiguous {tuple(shape)} tensor of x's dtype on x's device")
+    return t
+
+
+def Eval(model: "JitModel", x: torch.Tensor, jac: bool = True, ctx: Optional[Context] = None, *,
+         res_out: Optional[torch.Tensor] = None, J_out: Optional[torch.Tensor] = None):
+    """``diff::Eval(x, f)`` (diff/auto_diff.h:14-138) for a bound run-time model at x [P, xdim]: returns (res [P, m], J [P, m, n]),
+    m = items x residuals_per_item in the row order of ``accumulate``; J is None with ``jac=False`` (the body then runs on plain
+    scalars).  ``kind="residual"`` bodies are differentiated on Jets, ``kind="accumulate"`` bodies bring their own rows, a
+    ``diff=`` model gives the reference's ``NumEval``.  On ``manifold="se3"`` / ``"user"`` J is over the tangent (n columns).
+    Not for scalar costs (``accumulate`` already returns their value and gradient) and not with a loss set.  ``res_out`` /
+    ``J_out``: write into the caller's tensors (views are fine as long as they are contiguous).  The first call of a model
+    compiles its Eval kernels (then cached)."""
+    if not isinstance(model, JitModel):
+        raise TypeError("Eval takes a bound run-time model (JitResidual.bind)")
+    _check_call(x, model)
+    ctx = ctx or default_context(x.device.index)
+    P = x.shape[0]
+    res = _eval_out(res_out, (P, model.m), x, "res_out")
+    J = _eval_out(J_out, (P, model.m, model.n), x, "J_out") if jac else None
+    _apply_loss(ctx, model)
+    check(ctx.lib.toa_jit_eval(ctx.h, model.res._h, model.items, P, model.packed.data_ptr(), x.data_ptr(), res.data_ptr(),
+                               J.data_ptr() if jac else None))
+    return res, J
+
+
+def CalculateJac(model: "JitModel", x: torch.Tensor, ctx: Optional[Context] = None, *, J_out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``diff::CalculateJac(x, f)`` (diff/auto_diff.h:120-138): the Jacobian rows J [P, m, n] alone (see ``Eval``)."""
+    if not isinstance(model, JitModel):
+        raise TypeError("CalculateJac takes a bound run-time model (JitResidual.bind)")
+    _check_call(x, model)
+    ctx = ctx or default_context(x.device.index)
+    P = x.shape[0]
+    J = _eval_out(J_out, (P, model.m, model.n), x, "J_out")
+    _apply_loss(ctx, model)
+    check(ctx.lib.toa_jit_eval(ctx.h, model.res._h, model.items, P, model.packed.data_ptr(), x.data_ptr(), None, J.data_ptr()))
+    return J
+
+
 def solve_damped(H: torch.Tensor, g: torch.Tensor, scale: float = 1.0, ctx: Optional[Context] = None):
     """SolverLM damping (lm.h:108-117, H_ii *= scale) + SolverGN::Solve (gn.h:150-171) for a batch.
     Returns (dx [P,n], ok [P] int32)."""

@@ -634,6 +634,40 @@ int toa_jit_lm_step(toa_handle h, toa_jit_model model, int num_items, int64_t P,
 int toa_jit_lm_stop(toa_handle h, toa_jit_model model, int num_items, int64_t P, const void* data_dev, void* x_dev,
                     const toa_options* options, const toa_results* results, uint64_t* counters_dev, void* state_dev,
                     const int32_t* stop_request_dev);
+/*      Ragged batches of a run-time model: every problem has its own item count (the reference solves one problem per call, so for
+ *      it every problem has its own size).  One data form at every layer:
+ *        data_dev          [total_items][scalars_per_item]   the items of all problems, one problem after another
+ *        header_dev        [P][header_scalars]               NULL when the model has no header
+ *        item_offsets_dev  int64 [P + 1]                     non-decreasing, [0] = 0, [P] = total_items: problem p owns items
+ *                                                            [off[p], off[p + 1])
+ *      max_items: the largest count, which the CALLER knows (the host never reads the offsets: no synchronisation).  The per-problem
+ *      limits of the uniform calls (items and Jacobian of one problem below 4 GiB, rows below 2^31) are judged against it, and the
+ *      kernels clamp every range into [0, total_items) and every count to max_items: a damaged offsets array reads nothing outside
+ *      data_dev (and an entry of the queue order is clamped into [0, P)).  data_dev may be NULL when total_items is 0.  A count of 0 is legal: that problem ends with TOA_STOP_SKIPPED, x untouched, no residuals (optimizer.h:373-377).
+ *      Each call mirrors its uniform twin — the same refusals (a cost model on LM, a loss on Eval, null pointers, another device's
+ *      model), P == 0 returns TOA_OK — and computes, for every problem, bit for bit what the twin computes for that problem
+ *      alone with num_items = its count.  The run calls always take the one-launch form (one wavefront per problem; no row-split)
+ *      and hand the problems out LONGEST FIRST: an order[P] array is built on the device (histogram over floor(log2(count)),
+ *      scan, scatter: stream-ordered, capturable, in the handle's workspace) so that a long problem never starts last.
+ *      TOA_RAGGED_KEEP_ORDER in `flags` hands them out in index order instead.  toa_jit_eval_ragged concatenates its outputs like
+ *      the items: res [total_items * kR], J [total_items * kR][n].  The kernels are one more code object per model (and per
+ *      M-estimator variant), built on first use and cached on disk; that first call is refused under stream capture. */
+#define TOA_RAGGED_KEEP_ORDER 1u
+int toa_jit_lm_run_ragged(toa_handle h, toa_jit_model model, const int64_t* item_offsets_dev, const void* header_dev, int max_items,
+                          int64_t total_items, int64_t P, const void* data_dev, void* x_dev, const toa_options* options,
+                          const toa_results* results, uint64_t* counters_dev, uint32_t flags);
+int toa_jit_gd_run_ragged(toa_handle h, toa_jit_model model, const int64_t* item_offsets_dev, const void* header_dev, int max_items,
+                          int64_t total_items, int64_t P, const void* data_dev, void* x_dev, const toa_options* options,
+                          const toa_gd_options* gd, const toa_results* results, uint64_t* counters_dev, uint32_t flags);
+int toa_jit_accumulate_ragged(toa_handle h, toa_jit_model model, const int64_t* item_offsets_dev, const void* header_dev, int max_items,
+                              int64_t total_items, int64_t P, const void* data_dev, const void* x_dev, int want_grad, void* g_dev,
+                              void* H_dev, double* cost_dev, int32_t* nres_dev);
+int toa_jit_eval_ragged(toa_handle h, toa_jit_model model, const int64_t* item_offsets_dev, const void* header_dev, int max_items,
+                        int64_t total_items, int64_t P, const void* data_dev, const void* x_dev, void* res_dev, void* J_dev);
+/*      toa_jit_model_stats of the ragged fused kernel (the plain L2 build, made on this call if it was not yet).  The ragged object is
+ *      built once, under the #defines of the uniform build that was kept (they fix the stage geometry, hence the bits); it carries a few
+ *      registers more than its uniform twin and is NOT re-tried when it spills: look here when a ragged run is slower than expected. */
+int toa_jit_model_stats_ragged(toa_handle h, toa_jit_model m, int* wg_per_cu, int* num_regs, int* scratch_bytes);
 
 /* ---- C1: the result gather of a sharded batch (SURVEY §8(b) export list `gather(handle_group...)`, §8(e)).
  *      Problems are independent (the reference optimises exactly one x per call, docs/API.md:12), so a batch of P_total

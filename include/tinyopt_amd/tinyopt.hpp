@@ -346,6 +346,8 @@ inline int to_pod(Method m) { return m == kForward ? TOA_DIFF_NUM_FORWARD : (m =
 template <typename Scalar>
 class JitModel;
 template <typename Scalar>
+class RaggedJitModel;
+template <typename Scalar>
 class JitResidual {
  public:
   // manifold: TOA_MANIFOLD_EUCLID, or TOA_MANIFOLD_SE3 — x is ONE pose stored as 12 scalars (R row-major, t), n = 6, the body reads
@@ -380,6 +382,11 @@ class JitResidual {
   JitResidual& operator=(const JitResidual&) = delete;
   // data: [P][header_scalars + items * item_scalars] host scalars
   JitModel<Scalar> bind(int64_t P, int items, const Scalar* data) const { return JitModel<Scalar>(*this, P, items, data); }
+  // A RAGGED batch: counts[p] items for problem p (0 is legal: that problem ends with kSkipped); data: [sum of counts][item_scalars]
+  // host scalars, the items of all problems one after another; header: [P][header_scalars] (null without a header).
+  RaggedJitModel<Scalar> bind_ragged(const std::vector<int64_t>& counts, const Scalar* data, const Scalar* header = nullptr) const {
+    return RaggedJitModel<Scalar>(*this, counts, data, header);
+  }
   const std::string& compile_log() const { return log_; }
   toa_jit_model handle() const { return h_; }
   const Context& ctx() const { return *ctx_; }
@@ -428,7 +435,56 @@ class JitModel : public LossTag {
   int items_;
   DeviceBuffer<Scalar> data_;
 };
+// A JitResidual bound to a ragged batch (toa_jit_*_ragged): taken by Optimize (LM, GN; GradientDescent for cost kinds), diff::Eval
+// and diff::CalculateJac, whose outputs are concatenated like the items.  One-launch form only: no host controls (stop callbacks,
+// max_duration_ms, the log line), no stepping Optimizer, no diff::CheckGradient.
+template <typename Scalar>
+class RaggedJitModel : public LossTag {
+ public:
+  RaggedJitModel(const JitResidual<Scalar>& res, const std::vector<int64_t>& counts, const Scalar* host, const Scalar* header)
+      : res_(&res), P_(int64_t(counts.size())), offsets_host_(counts.size() + 1, 0) {
+    for (size_t p = 0; p < counts.size(); ++p) {
+      if (counts[p] < 0) throw std::invalid_argument("tinyopt_amd::bind_ragged: a count is negative");
+      if (counts[p] * res.residuals_per_item() >= (int64_t(1) << 31)) throw std::invalid_argument("tinyopt_amd::bind_ragged: a problem has 2^31 residual rows or more");
+      offsets_host_[p + 1] = offsets_host_[p] + counts[p];
+      if (counts[p] > max_items_) max_items_ = int(counts[p]);
+    }
+    if (res.header_scalars() > 0 && !header) throw std::invalid_argument("tinyopt_amd::bind_ragged: the model has header scalars: header must not be null");
+    offsets_ = DeviceBuffer<int64_t>(res.ctx(), offsets_host_.size());
+    offsets_.upload(offsets_host_.data());
+    const size_t elems = size_t(total_items()) * size_t(res.item_scalars());
+    data_ = DeviceBuffer<Scalar>(res.ctx(), std::max<size_t>(1, elems));   // (never a null data pointer, even without items)
+    if (elems > 0) data_.upload(host);
+    if (res.header_scalars() > 0) {
+      header_ = DeviceBuffer<Scalar>(res.ctx(), std::max<size_t>(1, size_t(P_) * res.header_scalars()));
+      if (P_ > 0) header_.upload(header);
+    }
+  }
+  static constexpr int model_id = -1;
+  int64_t P() const { return P_; }
+  int n() const { return res_->n(); }
+  int xdim() const { return res_->xdim(); }
+  int max_items() const { return max_items_; }
+  int64_t total_items() const { return offsets_host_.back(); }
+  int64_t rows() const { return total_items() * res_->residuals_per_item(); }   // residual rows of the whole batch
+  const std::vector<int64_t>& offsets() const { return offsets_host_; }
+  const int64_t* offsets_dev() const { return offsets_.data(); }
+  const Scalar* data() const { return data_.data(); }
+  const Scalar* header() const { return res_->header_scalars() > 0 ? header_.data() : nullptr; }
+  const Context& ctx() const { return res_->ctx(); }
+  toa_jit_model ragged_handle() const { return res_->handle(); }
+
+ private:
+  const JitResidual<Scalar>* res_;
+  int64_t P_;
+  int max_items_ = 0;
+  std::vector<int64_t> offsets_host_;
+  DeviceBuffer<int64_t> offsets_;
+  DeviceBuffer<Scalar> data_, header_;
+};
 namespace detail {
+template <typename C, typename = void> struct is_ragged : std::false_type {};
+template <typename C> struct is_ragged<C, std::void_t<decltype(std::declval<const C&>().ragged_handle())>> : std::true_type {};
 template <typename C, typename = void> struct is_jit : std::false_type {};
 template <typename C> struct is_jit<C, std::void_t<decltype(std::declval<const C&>().jit_handle())>> : std::true_type {};
 }  // namespace detail
@@ -460,12 +516,19 @@ struct Output {
   bool Converged() const { return stop_reason >= kMinError && stop_reason < kMaxIters; }
 };
 
+// In which order the persistent kernel hands out the problems of a ragged batch (Optimize's last argument).
+enum class QueueOrder { kLongestFirst = 0, kKeepOrder };
+
 template <typename Scalar, typename Cost>
 BatchOutput OptimizeWithHostControls(std::vector<Scalar>& x, const Cost& cost, const Options& options, bool history);
 
 // tinyopt::Optimize(x, cost, options) for a batch.  x: [P][n] contiguous host scalars, updated in place.
+// order (ragged batches only): QueueOrder::kKeepOrder hands the problems out in index order instead of longest first
+// (TOA_RAGGED_KEEP_ORDER); a type of its own, so that it cannot be passed where `history` goes.
 template <typename Scalar, typename Cost>
-BatchOutput Optimize(std::vector<Scalar>& x, const Cost& cost, const Options& options = {}, bool history = false) {
+BatchOutput Optimize(std::vector<Scalar>& x, const Cost& cost, const Options& options = {}, bool history = false,
+                     QueueOrder order = QueueOrder::kLongestFirst) {
+  const bool keep_order = order == QueueOrder::kKeepOrder;
   const int64_t P = cost.P();
   const int n = cost.n();
   if (int64_t(x.size()) != P * cost.xdim())
@@ -479,8 +542,15 @@ BatchOutput Optimize(std::vector<Scalar>& x, const Cost& cost, const Options& op
       throw std::invalid_argument("tinyopt_amd::Optimize: a numerically differentiated model runs as one launch per solve: stop callbacks, "
                                   "max_duration_ms and the log line are not supported (it has no stepping form)");
   }
-  if (options.has_host_controls()) {
-    return OptimizeWithHostControls(x, cost, options, history);   // (run-time models too: toa_jit_lm_begin / step / stop)
+  if constexpr (detail::is_ragged<Cost>::value) {
+    if (options.has_host_controls())
+      throw std::invalid_argument("tinyopt_amd::Optimize: a ragged batch (bind_ragged) runs in the one-launch form only: no stepping form, so "
+                                  "no host controls (stop callbacks, max_duration_ms, the log line)");
+  } else {
+    if (keep_order) throw std::invalid_argument("tinyopt_amd::Optimize: keep_order is the queue order of a ragged batch (bind_ragged)");
+    if (options.has_host_controls()) {
+      return OptimizeWithHostControls(x, cost, options, history);   // (run-time models too: toa_jit_lm_begin / step / stop)
+    }
   }
   const Context& ctx = cost.ctx();
   DeviceBuffer<Scalar> dx(ctx, x.size());
@@ -507,7 +577,17 @@ BatchOutput Optimize(std::vector<Scalar>& x, const Cost& cost, const Options& op
   }
   const toa_options pod = options.to_pod();
   apply_loss(cost);
-  if constexpr (detail::is_jit<Cost>::value) {
+  if constexpr (detail::is_ragged<Cost>::value) {
+    const uint32_t flags = keep_order ? TOA_RAGGED_KEEP_ORDER : 0u;
+    if (gd) {
+      const toa_gd_options gpod = options.gd_pod();
+      check(toa_jit_gd_run_ragged(ctx.get(), cost.ragged_handle(), cost.offsets_dev(), cost.header(), cost.max_items(), cost.total_items(), P,
+                                  cost.data(), dx.data(), &pod, &gpod, &r, nullptr, flags));
+    } else {
+      check(toa_jit_lm_run_ragged(ctx.get(), cost.ragged_handle(), cost.offsets_dev(), cost.header(), cost.max_items(), cost.total_items(), P,
+                                  cost.data(), dx.data(), &pod, &r, nullptr, flags));
+    }
+  } else if constexpr (detail::is_jit<Cost>::value) {
     if (gd) {   // gd::Optimizer on a scalar cost model (the library refuses any other model: optimize.h:59-75)
       const toa_gd_options gpod = options.gd_pod();
       check(toa_jit_gd_run(ctx.get(), cost.jit_handle(), cost.items(), P, cost.data(), dx.data(), &pod, &gpod, &r, nullptr));
@@ -563,6 +643,10 @@ GradientCheck CheckGradient(const JitModel<Scalar>& model, const std::vector<Sca
   return out;
 }
 
+// a ragged batch has no gradient checker: check the model on a uniform batch (JitResidual::bind)
+template <typename Scalar>
+GradientCheck CheckGradient(const RaggedJitModel<Scalar>&, const std::vector<Scalar>&, double = 0.0, Method = kCentral, bool = true) = delete;
+
 // diff::Eval / diff::CalculateJac (diff/auto_diff.h:14-138) for a bound run-time residual model at x [P][xdim]: the residuals
 // [P][m] and the Jacobian rows [P][m][n], row-major, m = items x residuals_per_item in the row order of the Accumulate seam; on a
 // manifold J is over the tangent.  A numeric model (JitResidual's diff argument) gives NumEval / EstimateNumJac.  Not for scalar
@@ -604,6 +688,31 @@ std::vector<Scalar> CalculateJac(const JitModel<Scalar>& model, const std::vecto
   J.download(out.data());
   return out;
 }
+// ... and for a ragged batch: the outputs concatenated like the items — res [rows], J [rows][n], rows = total_items x residuals_per_item.
+template <typename Scalar>
+std::pair<std::vector<Scalar>, std::vector<Scalar>> Eval(const RaggedJitModel<Scalar>& model, const std::vector<Scalar>& x, bool jac = true, bool res = true) {
+  const int64_t P = model.P();
+  if (int64_t(x.size()) != P * model.xdim())
+    throw std::invalid_argument("tinyopt_amd::diff::Eval: x must hold P * (parameters per problem) scalars");
+  const Context& ctx = model.ctx();
+  const size_t rows = size_t(model.rows());
+  DeviceBuffer<Scalar> dx(ctx, std::max<size_t>(1, x.size()));
+  if (!x.empty()) dx.upload(x.data());
+  DeviceBuffer<Scalar> rbuf(ctx, std::max<size_t>(1, rows));
+  DeviceBuffer<Scalar> J(ctx, jac ? std::max<size_t>(1, rows * size_t(model.n())) : size_t(1));
+  apply_loss(model);
+  check(toa_jit_eval_ragged(ctx.get(), model.ragged_handle(), model.offsets_dev(), model.header(), model.max_items(), model.total_items(), P,
+                            model.data(), dx.data(), res ? rbuf.data() : nullptr, jac ? J.data() : nullptr));
+  check(toa_synchronize(ctx.get()));
+  std::pair<std::vector<Scalar>, std::vector<Scalar>> out;
+  if (res && rows) { std::vector<Scalar> t(rbuf.size()); rbuf.download(t.data()); out.first.assign(t.begin(), t.begin() + rows); }
+  if (jac && rows) { std::vector<Scalar> t(J.size()); J.download(t.data()); out.second.assign(t.begin(), t.begin() + rows * size_t(model.n())); }
+  return out;
+}
+template <typename Scalar>
+std::vector<Scalar> CalculateJac(const RaggedJitModel<Scalar>& model, const std::vector<Scalar>& x) {
+  return Eval(model, x, true, false).second;
+}
 }  // namespace diff
 
 // The reference's class / stepping form (`lm::Optimizer<H_t> optimizer(options)`; `optimizer.Step(x, acc, out)` one loop
@@ -611,6 +720,8 @@ std::vector<Scalar> CalculateJac(const JitModel<Scalar>& model, const std::vecto
 // x stays on the device between steps; `x()` downloads the current iterate, `output()` the results so far.
 template <typename Scalar, typename Cost>
 class Optimizer {
+  static_assert(!detail::is_ragged<Cost>::value, "a ragged batch (bind_ragged) runs in the one-launch form only: no stepping Optimizer");
+
  public:
   Optimizer(std::vector<Scalar>& x, const Cost& cost, const Options& options = {}, bool history = false)
       : x_(&x), cost_(&cost), options_(options), pod_(options.to_pod()), P_(cost.P()), n_(cost.n()),

@@ -135,6 +135,13 @@ PROTOTYPES = {
     "toa_jit_accumulate": (C.c_int, [_P, _P, C.c_int, C.c_int64, _P, _P, C.c_int, _P, _P, _P, _P]),
     "toa_jit_check_gradient": (C.c_int, [_P, _P, C.c_int, C.c_int64, _P, _P, C.c_double, C.c_int, C.c_int, _P, _P]),
     "toa_jit_eval": (C.c_int, [_P, _P, C.c_int, C.c_int64, _P, _P, _P, _P]),
+    "toa_jit_lm_run_ragged": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int64, C.c_int64, _P, _P, C.POINTER(ToaOptions), C.POINTER(ToaResults), _P,
+                                        C.c_uint32]),
+    "toa_jit_gd_run_ragged": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int64, C.c_int64, _P, _P, C.POINTER(ToaOptions), C.POINTER(ToaGdOptions),
+                                        C.POINTER(ToaResults), _P, C.c_uint32]),
+    "toa_jit_accumulate_ragged": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int64, C.c_int64, _P, _P, C.c_int, _P, _P, _P, _P]),
+    "toa_jit_eval_ragged": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int64, C.c_int64, _P, _P, _P, _P]),
+    "toa_jit_model_stats_ragged": (C.c_int, [_P, _P, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "toa_gd_options_default": (None, [C.POINTER(ToaGdOptions)]),
     "toa_jit_gd_run": (C.c_int, [_P, _P, C.c_int, C.c_int64, _P, _P, C.POINTER(ToaOptions), C.POINTER(ToaGdOptions), C.POINTER(ToaResults), _P]),
     "toa_jit_lm_run_split": (C.c_int, [_P, _P, C.c_int, C.c_int64, _P, _P, C.POINTER(ToaOptions), C.POINTER(ToaResults), _P, C.c_int]),

@@ -564,6 +564,18 @@ class JitResidual:
         data = None for a functor with item_scalars = 0 (e.g. a pose prior: everything is in the header)."""
         return JitModel(self, data, header, items)
 
+    def bind_ragged(self, data: torch.Tensor, counts=None, offsets=None, header: Optional[torch.Tensor] = None) -> "RaggedJitModel":
+        """A RAGGED batch: every problem has its own item count.  data: [total_items, item_scalars] on the GPU, the items of all
+        problems one after another; exactly one of ``counts`` ([P] items per problem) / ``offsets`` ([P + 1], see ``ragged_offsets``);
+        header: [P, header_scalars].  A count of 0 is legal (that problem ends with kSkipped, x untouched)."""
+        return RaggedJitModel(self, data, counts, offsets, header)
+
+    def stats_ragged(self) -> dict:
+        """``stats`` of the ragged fused kernel (its plain L2 build, compiled by this call if it was not yet)."""
+        v = [C.c_int(0) for _ in range(3)]
+        check(self.ctx.lib.toa_jit_model_stats_ragged(self.ctx.h, self._h, *[C.byref(t) for t in v]))
+        return dict(wg_per_cu=v[0].value, num_regs=v[1].value, scratch_bytes=v[2].value)
+
     def close(self) -> None:
         if self._h:
             self.ctx.lib.toa_model_destroy(self._h)
@@ -598,6 +610,84 @@ class JitModel(_LossMixin):
     @property
     def algorithmic_bytes_per_pass(self) -> int:
         return self.packed.shape[1] * self.packed.element_size()
+
+
+def ragged_offsets(counts=None, offsets=None, total_items: Optional[int] = None) -> torch.Tensor:
+    """The offsets array of a ragged batch (``JitResidual.bind_ragged``), validated on the CPU: int64 [P + 1], non-decreasing,
+    [0] = 0, [P] = total_items; problem p owns items [off[p], off[p + 1]).  Exactly one of ``counts`` ([P], each >= 0) and
+    ``offsets`` ([P + 1]) is given; ``total_items``, when given, must be the sum.  Raises ValueError with the reason."""
+    if (counts is None) == (offsets is None):
+        raise ValueError("ragged_offsets: give exactly one of counts / offsets")
+    src = counts if counts is not None else offsets
+    t = src.detach().to("cpu") if isinstance(src, torch.Tensor) else torch.as_tensor(list(src))
+    if t.numel() and (t.is_floating_point() or t.is_complex() or t.dtype == torch.bool):
+        raise ValueError("ragged_offsets: counts / offsets must be integers")
+    t = t.to(torch.int64).reshape(-1)
+    if counts is not None:
+        if bool((t < 0).any()):
+            raise ValueError("ragged_offsets: a count is negative")
+        off = torch.zeros(t.numel() + 1, dtype=torch.int64)
+        off[1:] = torch.cumsum(t, 0)
+    else:
+        if t.numel() < 1:
+            raise ValueError("ragged_offsets: offsets has P + 1 entries (at least one)")
+        if int(t[0]) != 0:
+            raise ValueError("ragged_offsets: offsets[0] must be 0")
+        if bool((t[1:] < t[:-1]).any()):
+            raise ValueError("ragged_offsets: offsets must be non-decreasing")
+        off = t.clone()
+    if total_items is not None and int(off[-1]) != int(total_items):
+        raise ValueError(f"ragged_offsets: the counts add up to {int(off[-1])} items, not total_items = {int(total_items)}")
+    return off
+
+
+class RaggedJitModel(_LossMixin):
+    """A JitResidual bound to a RAGGED batch: data [total_items, item_scalars] (the items of all problems, one after another), a
+    separate header [P, header_scalars] and int64 offsets [P + 1].  Taken by ``Optimize`` (LM, GN; GradientDescent for cost kinds),
+    ``accumulate``, ``Eval`` and ``CalculateJac``; every problem computes bit for bit what it would alone in a uniform batch of
+    its own count.  No ``splits``, no host controls (stop callbacks, max_duration_ms, the log line), no ``Optimizer`` (stepping)
+    and no ``CheckGradient``: a ragged batch runs in the one-launch form only."""
+    model_id = None
+
+    def __init__(self, res: JitResidual, data: torch.Tensor, counts=None, offsets=None, header: Optional[torch.Tensor] = None):
+        if data.dim() != 2 or data.shape[1] != res.kD or not data.is_cuda or data.dtype != res.dtype:
+            raise ValueError("bind_ragged: data must be a [total_items, item_scalars] GPU tensor of the model's dtype")
+        off = ragged_offsets(counts, offsets, total_items=data.shape[0])
+        self.res = res
+        self.P, self.n, self.xdim, self.dtype = off.numel() - 1, res.n, res.xdim, res.dtype
+        self.total_items = int(data.shape[0])
+        cnt = off[1:] - off[:-1]
+        self.max_items = int(cnt.max()) if self.P else 0
+        if self.max_items * res.kR >= 2 ** 31:
+            raise ValueError("bind_ragged: a problem has 2^31 residual rows or more")
+        self.offsets_host = off
+        self.offsets = off.to(data.device)
+        self.data = data.contiguous()
+        if res.kH:
+            if header is None or tuple(header.shape) != (self.P, res.kH) or header.dtype != res.dtype or header.device != data.device:
+                raise ValueError("bind_ragged: header must be a [P, header_scalars] tensor of the model's dtype on data's device")
+            self.header = header.contiguous()
+        else:
+            self.header = None
+
+    @property
+    def rows(self) -> int:
+        """Residual rows of the whole batch: total_items x residuals_per_item."""
+        return self.total_items * self.res.kR
+
+    @property
+    def algorithmic_bytes_per_pass(self) -> float:
+        """The mean per problem."""
+        if not self.P:
+            return 0.0
+        return (self.total_items * self.res.kD / self.P + self.res.kH) * self.data.element_size()
+
+    def _ragged_args(self):
+        return (self.offsets.data_ptr(), self.header.data_ptr() if self.header is not None else None, self.max_items, self.total_items)
+
+
+def _refuse_ragged(what: str):
+    raise ValueError(f"a ragged batch (bind_ragged) runs in the one-launch form only: {what}")
 
 
 class SE3Prior:
@@ -735,7 +825,7 @@ class DenseRowNatural(_LossMixin):
         return self.m * (self.n + 1) * self.packed.element_size()
 
 
-_MODELS = (BundleAdjustmentLists, JitModel, TestFn, MahaPrior, SE3Prior, DenseRow, GaussianPrior, Sqrt2, SE3Reproj, CircleFit, DenseRowAD6, DenseRowAD, DenseRowNatural, BundleAdjustment)
+_MODELS = (BundleAdjustmentLists, JitModel, RaggedJitModel, TestFn, MahaPrior, SE3Prior, DenseRow, GaussianPrior, Sqrt2, SE3Reproj, CircleFit, DenseRowAD6, DenseRowAD, DenseRowNatural, BundleAdjustment)
 
 
 @dataclass
@@ -827,7 +917,7 @@ def _results_pod(out: Output) -> ToaResults:
 
 def Optimize(x: torch.Tensor, cost, options: Optional[Options] = None, *, history: bool = False,
              ctx: Optional[Context] = None, out: Optional[Output] = None, splits: Optional[int] = None,
-             zero_counters: bool = True) -> Output:
+             zero_counters: bool = True, keep_order: bool = False) -> Output:
     """``tinyopt::Optimize(x, cost, options)`` (optimize.h:16-77) for a batch of independent problems.
 
     x: [P, n] GPU tensor, updated IN PLACE (the reference takes x by non-const reference).
@@ -836,11 +926,16 @@ def Optimize(x: torch.Tensor, cost, options: Optional[Options] = None, *, histor
     when the solve is done (it enqueues two passes ahead of the stop counts where every stage is a kernel of this library).  ``out.counters`` is zeroed here and added to by the
     library (every path accumulates); ``zero_counters=False`` skips that fill launch for a caller whose ``out`` is fresh or who
     wants running totals (it is ~8 us of a 50 us single-problem solve; the C-ABI takes the counters as they are).
+    ``keep_order`` (ragged batches only): hand the problems out in index order instead of longest first.
     """
     options = options or Options()
     _check_call(x, cost)
     P, n = x.shape[0], cost.n
     ctx = ctx or default_context(x.device.index)
+    if isinstance(cost, RaggedJitModel):
+        return _optimize_ragged(x, cost, options, history, ctx, out, splits, zero_counters, keep_order)
+    if keep_order:
+        raise ValueError("keep_order is the queue order of a ragged batch (JitResidual.bind_ragged)")
     if isinstance(cost, BundleAdjustment):
         if options.has_host_controls() or splits is not None:
             raise ValueError("BundleAdjustment runs as one launch per solve: no stop callbacks / splits")
@@ -949,6 +1044,42 @@ def _optimize_gd(x: torch.Tensor, cost: "JitModel", options: Options, history: b
     return out
 
 
+def _optimize_ragged(x: torch.Tensor, cost: "RaggedJitModel", options: Options, history: bool, ctx: Context, out: Optional[Output],
+                     splits: Optional[int], zero_counters: bool, keep_order: bool) -> Output:
+    """One launch of toa_jit_lm_run_ragged (LM / GN) or toa_jit_gd_run_ragged (GradientDescent on a cost kind)."""
+    if splits is not None:
+        _refuse_ragged("no row-split form (splits)")
+    if options.has_host_controls():
+        _refuse_ragged("no stepping form, so no host controls (stop callbacks, max_duration_ms, the log line)")
+    P = x.shape[0]
+    gd_run = cost.res.kind in JitResidual.COST_KINDS and options.solver_type == Options.GradientDescent
+    pod = options.to_pod()
+    if out is None:
+        o2 = options
+        if gd_run:
+            import copy
+            o2 = copy.deepcopy(options)
+            o2.hessian.save_last = False
+        out = _alloc_output(P, cost.n, o2, history, x.device)
+    elif zero_counters:
+        out.counters.zero_()
+    res = _results_pod(out)
+    _apply_loss(ctx, cost)
+    flags = 1 if keep_order else 0
+    if gd_run:
+        from ._capi import ToaGdOptions
+        gd = ToaGdOptions()
+        ctx.lib.toa_gd_options_default(C.byref(gd))
+        gd.lr = float(options.gd.lr)
+        res.final_hessian = None
+        check(ctx.lib.toa_jit_gd_run_ragged(ctx.h, cost.res._h, *cost._ragged_args(), P, cost.data.data_ptr(), x.data_ptr(), C.byref(pod),
+                                            C.byref(gd), C.byref(res), out.counters.data_ptr(), flags))
+    else:
+        check(ctx.lib.toa_jit_lm_run_ragged(ctx.h, cost.res._h, *cost._ragged_args(), P, cost.data.data_ptr(), x.data_ptr(), C.byref(pod),
+                                            C.byref(res), out.counters.data_ptr(), flags))
+    return out
+
+
 class Optimizer:
     """The reference's class / stepping form: ``lm::Optimizer<H_t> optimizer(options)`` then ``optimizer.Step(x, acc, out)``
     one loop pass at a time (optimizer.h:199,331-539), or ``optimizer(x, cost, max_iters)`` for a bounded run — for a
@@ -959,6 +1090,8 @@ class Optimizer:
                  ctx: Optional[Context] = None):
         self.options = options or Options()
         _check_call(x, cost)
+        if isinstance(cost, RaggedJitModel):
+            _refuse_ragged("no stepping form (Optimizer)")
         if isinstance(cost, JitModel) and cost.res.diff != "ad":
             raise ValueError("a numerically differentiated model (diff=...) has no stepping form")
         self.x, self.cost = x, cost
@@ -1159,6 +1292,12 @@ def accumulate(cost, x: torch.Tensor, want_grad: bool = True, ctx: Optional[Cont
     c = torch.zeros(P, dtype=torch.float64, device=dev)
     nres = torch.zeros(P, dtype=torch.int32, device=dev)
     _apply_loss(ctx, cost)
+    if isinstance(cost, RaggedJitModel):   # (a problem without items: zeros, nres = 0)
+        is_cost = cost.res.kind in JitResidual.COST_KINDS
+        check(ctx.lib.toa_jit_accumulate_ragged(ctx.h, cost.res._h, *cost._ragged_args(), P, cost.data.data_ptr(), x.data_ptr(), int(want_grad),
+                                                g.data_ptr() if want_grad else None, H.data_ptr() if want_grad and not is_cost else None,
+                                                c.data_ptr(), nres.data_ptr()))
+        return g, (None if is_cost else H), c, nres
     if isinstance(cost, JitModel) and cost.res.kind in JitResidual.COST_KINDS:   # SolverGD::Build: g and the cost, no H
         check(ctx.lib.toa_jit_accumulate(ctx.h, cost.res._h, cost.items, P, cost.packed.data_ptr(), x.data_ptr(), int(want_grad),
                                          g.data_ptr() if want_grad else None, None, c.data_ptr(), nres.data_ptr()))
@@ -1193,6 +1332,8 @@ def CheckGradient(model: "JitModel", x: torch.Tensor, eps: Optional[float] = Non
     x [P, n]: the model's own derivatives against finite differences of its residuals (or cost terms) with step eps / 10.
     Residual kinds compare g = J^T r and, with ``check_H``, H = J^T J; cost kinds compare g.  ``eps`` None: the reference's default
     (1e-2 in float32, 1e-5 in float64).  The first check of a model with a (method, eps) compiles its numeric twin (then cached)."""
+    if isinstance(model, RaggedJitModel):
+        _refuse_ragged("no CheckGradient (check the model on a uniform batch: JitResidual.bind)")
     if not isinstance(model, JitModel):
         raise TypeError("CheckGradient takes a bound run-time model (JitResidual.bind)")
     if method not in ("forward", "central", "fast_central"):
@@ -1228,6 +1369,15 @@ def Eval(model: "JitModel", x: torch.Tensor, jac: bool = True, ctx: Optional[Con
     Not for scalar costs (``accumulate`` already returns their value and gradient) and not with a loss set.  ``res_out`` /
     ``J_out``: write into the caller's tensors (views are fine as long as they are contiguous).  The first call of a model
     compiles its Eval kernels (then cached)."""
+    if isinstance(model, RaggedJitModel):   # outputs concatenated like the items: res [rows], J [rows, n]
+        _check_call(x, model)
+        ctx = ctx or default_context(x.device.index)
+        res = _eval_out(res_out, (model.rows,), x, "res_out")
+        J = _eval_out(J_out, (model.rows, model.n), x, "J_out") if jac else None
+        _apply_loss(ctx, model)
+        check(ctx.lib.toa_jit_eval_ragged(ctx.h, model.res._h, *model._ragged_args(), x.shape[0], model.data.data_ptr(), x.data_ptr(),
+                                          res.data_ptr(), J.data_ptr() if jac else None))
+        return res, J
     if not isinstance(model, JitModel):
         raise TypeError("Eval takes a bound run-time model (JitResidual.bind)")
     _check_call(x, model)
@@ -1243,6 +1393,14 @@ def Eval(model: "JitModel", x: torch.Tensor, jac: bool = True, ctx: Optional[Con
 
 def CalculateJac(model: "JitModel", x: torch.Tensor, ctx: Optional[Context] = None, *, J_out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """``diff::CalculateJac(x, f)`` (diff/auto_diff.h:120-138): the Jacobian rows J [P, m, n] alone (see ``Eval``)."""
+    if isinstance(model, RaggedJitModel):
+        _check_call(x, model)
+        ctx = ctx or default_context(x.device.index)
+        J = _eval_out(J_out, (model.rows, model.n), x, "J_out")
+        _apply_loss(ctx, model)
+        check(ctx.lib.toa_jit_eval_ragged(ctx.h, model.res._h, *model._ragged_args(), x.shape[0], model.data.data_ptr(), x.data_ptr(),
+                                          None, J.data_ptr()))
+        return J
     if not isinstance(model, JitModel):
         raise TypeError("CalculateJac takes a bound run-time model (JitResidual.bind)")
     _check_call(x, model)

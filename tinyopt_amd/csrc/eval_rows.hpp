@@ -78,7 +78,7 @@ struct EvalRowsTraits {
 
 template <typename T, typename RF, int MANIFOLD, bool WANT_J>
 __global__ void __launch_bounds__(256) eval_rows_kernel(const void* data_, const void* x_, long long P, int num_items, void* res_,
-                                                        void* J_, int ss_per_unit) {
+                                                        void* J_, int ss_per_unit TOA_RAGGED_KARG) {
   using TR = EvalRowsTraits<T, RF, MANIFOLD, WANT_J>;
   using RM = typename TR::RM;
   constexpr int kN = TR::kN, kR = TR::kR, kD = TR::kD, kH = TR::kH;
@@ -110,7 +110,24 @@ __global__ void __launch_bounds__(256) eval_rows_kernel(const void* data_, const
   for (long long u = (long long)blockIdx.x * 4 + wave; u < units; u += (long long)gridDim.x * 4) {
     const long long p = u / upp;
     const int ss0 = int(u - p * upp) * ss_per_unit;
+#ifdef TOA_RAGGED
+    // ragged batches (ragged.hpp): num_items is the LARGEST count — it sizes the units — and the problem's own range comes from the
+    // offsets; a unit that starts beyond its problem's last super-step has nothing to do.  Outputs are concatenated like the items.
+    const RaggedRange rr = ragged_range(rag, p);
+    const int nit = rr.count;
+    const long long nss_p = ((long long)nit + IT - 1) / IT;
+    if (ss0 >= nss_p) continue;
+    const int ss1 = int(nss_p < (long long)ss0 + ss_per_unit ? nss_p : (long long)ss0 + ss_per_unit);
+    const T* const d = static_cast<const T*>(rag.header) + size_t(p) * kH;
+    const T* const itemsp = data + size_t(rr.first) * kD;
+    const size_t row0 = size_t(rr.first) * kR;
+#else
+    const int nit = num_items;
     const int ss1 = int(nss < (long long)ss0 + ss_per_unit ? nss : (long long)ss0 + ss_per_unit);
+    const T* const d = data + size_t(p) * (size_t(kH) + size_t(num_items) * kD);
+    const T* const itemsp = d + kH;
+    const size_t row0 = size_t(p) * m;
+#endif
     if (p != pcur) {   // x, and the Jets of x (+) d: once per problem per wave
       wave_sync();
       xs[lane] = lane < XD ? X[size_t(p) * XD + lane] : T(0);
@@ -118,8 +135,7 @@ __global__ void __launch_bounds__(256) eval_rows_kernel(const void* data_, const
       if constexpr (kTable > 0) RF::build_table(xs, reinterpret_cast<typename RF::TabJet*>(stg + G.table_off), lane);
       pcur = p;
     }
-    const T* const d = data + size_t(p) * (size_t(kH) + size_t(num_items) * kD);
-    const i32x4 rsrc = make_rsrc(d + kH, unsigned(num_items) * unsigned(kD) * unsigned(sizeof(T)));
+    const i32x4 rsrc = make_rsrc(itemsp, unsigned(nit) * unsigned(kD) * unsigned(sizeof(T)));
     for (int ss = ss0; ss < ss1; ++ss) {
       // ---- the items of the super-step -> the region (its last readers, the previous copy-out, have their data: lgkmcnt)
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -130,7 +146,7 @@ __global__ void __launch_bounds__(256) eval_rows_kernel(const void* data_, const
       wave_sync();
       // ---- the functor, one item per lane
       const int item = ss * IT + lane;
-      const bool valid = lane < IT && item < num_items;
+      const bool valid = lane < IT && item < nit;
       T rv[kR];
       T Jv[WANT_J ? kR : 1][kN];
       if (valid) {
@@ -147,15 +163,15 @@ __global__ void __launch_bounds__(256) eval_rows_kernel(const void* data_, const
           else RF::template eval_manual<false>(xs, d, pp, rv, static_cast<T(*)[kN]>(nullptr));
         }
         if (R) {   // consecutive lanes, consecutive scalars
-          T* const ro = R + size_t(p) * m + size_t(item) * kR;
+          T* const ro = R + row0 + size_t(item) * kR;
 #pragma unroll
           for (int q = 0; q < kR; ++q) ro[q] = rv[q];
         }
       }
       if constexpr (WANT_J) {
         // ---- [J], dense, over the raw items; the image starts where a 16-byte boundary of memory is one of LDS
-        const int rows_here = int(min((long long)IT, (long long)num_items - (long long)ss * IT)) * kR;
-        T* const g0 = Jg + (size_t(p) * m + size_t(ss) * ROWS) * kN;       // the super-step's run in memory
+        const int rows_here = int(min((long long)IT, (long long)nit - (long long)ss * IT)) * kR;
+        T* const g0 = Jg + (row0 + size_t(ss) * ROWS) * kN;       // the super-step's run in memory
         const unsigned nbytes = unsigned(rows_here) * unsigned(kN) * unsigned(sizeof(T));
         const unsigned ph = unsigned(__builtin_amdgcn_readfirstlane(int(unsigned(reinterpret_cast<size_t>(g0)) & 15u)));
         unsigned char* const img = stg + ph;

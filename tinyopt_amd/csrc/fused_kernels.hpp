@@ -62,6 +62,13 @@ struct FusedParams {
   int reserved_[2];              // (the team form's two fields, round 5: the block's layout is unchanged)
 };
 
+// The parameter block of a ragged launch (ragged.hpp): the uniform block, then the ragged arguments.  The kernels take the
+// block by its first member's address; only the ragged code object reads behind it.
+struct RaggedFusedParams {
+  FusedParams f;
+  RaggedArgs ragged;
+};
+
 template <typename M, typename = void>
 struct ModelStageBytes { static constexpr size_t value = 0; };
 template <typename M>
@@ -133,6 +140,11 @@ __global__ void __launch_bounds__(64 * ModelWaves<Model>::value) TOA_FUSED_ATTR 
   Model model;
   model.init(n, prm_g->m, prm_g->data);
   model.set_loss(prm_g->loss, prm_g->loss_th2);
+#ifdef TOA_RAGGED
+  const RaggedArgs& rag = reinterpret_cast<const RaggedFusedParams*>(prm_g)->ragged;
+  model.set_ragged(rag);
+  const int* const order = rag.order;   // the q-th problem handed out (null: problem q)
+#endif
   if constexpr (ModelStageBytes<Model>::value > 0) model.stage = reinterpret_cast<unsigned char*>(smem) + size_t(wave) * prm_g->lds_per_wave + prm_g->stage_off;
   T* X = static_cast<T*>(prm_g->x);
   const int xd = Model::kXdim ? Model::kXdim : n;  // stored parameters per problem (SE3: 12 for n = 6)
@@ -183,6 +195,9 @@ __global__ void __launch_bounds__(64 * ModelWaves<Model>::value) TOA_FUSED_ATTR 
       }
       if (!ghost) break;
     }
+#ifdef TOA_RAGGED
+    if (order && !ghost) p = min(max(order[p], 0), int(P) - 1);   // (wave-uniform: a scalar load; clamped — a slot of a damaged order addresses no problem beyond the batch)
+#endif
     // Fairness between the waves of a SIMD.  The issue arbiter serves the OLDEST wave first, and a wave keeps its age for
     // the whole (persistent) kernel: the launch timeline shows the oldest wave of each SIMD solving a problem in 0.8 ms
     // while the youngest needs up to 6.9 ms for its first one and is still far from done when the queue runs dry — the
@@ -235,7 +250,7 @@ __global__ void __launch_bounds__(64 * ModelWaves<Model>::value) TOA_FUSED_ATTR 
 template <typename Model>
 __global__ void __launch_bounds__(256) accumulate_kernel(const void* data_, const void* x_, long long P, int n, int m,
                                                          int want_grad, void* g_, void* H_, double* cost, int* nres,
-                                                         int lds_per_wave, int loss, double loss_th2) {
+                                                         int lds_per_wave, int loss, double loss_th2 TOA_RAGGED_KARG) {
   using T = typename Model::Scalar;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -243,6 +258,9 @@ __global__ void __launch_bounds__(256) accumulate_kernel(const void* data_, cons
   Model model;
   model.init(n, m, data_);
   model.set_loss(loss, loss_th2);
+#ifdef TOA_RAGGED
+  model.set_ragged(rag);
+#endif
   WaveLds<T> L = WaveLds<T>::carve(model_bind_stage(model, smem + size_t(wave) * lds_per_wave, n), n);
   const int xd = Model::kXdim ? Model::kXdim : n;
   for (long long p = (long long)blockIdx.x * 4 + wave; p < P; p += (long long)gridDim.x * 4) {

@@ -27,6 +27,7 @@
 #include "gd_device.hpp"
 #include "jet.hpp"
 #include "wave_utils.hpp"
+#include "ragged.hpp"
 #include "num_diff.hpp"   // NumCostFunctor: a cost body differentiated by finite differences (toa_jit_spec::diff)
 
 namespace toa {
@@ -42,6 +43,12 @@ struct GdParams {
   int lds_per_wave;
   unsigned long long* counters;    // [TOA_NUM_COUNTERS] or null
   int* queue;                      // [0] pop counter, [16] waves that have left the kernel (lm_fused_kernel's protocol)
+};
+
+// a ragged launch's block (ragged.hpp, fused_kernels.hpp RaggedFusedParams)
+struct RaggedGdParams {
+  GdParams g;
+  RaggedArgs ragged;
 };
 
 // x as Jets of one chunk of columns [c0, c0 + CW), read from the wave's LDS copy (n > 12: a register array indexed by the
@@ -71,7 +78,20 @@ struct CostModel {
   const T* d;
   int items;
   __device__ __forceinline__ void init(int items_, const void* dp) { items = items_; data = static_cast<const T*>(dp); }
+#ifdef TOA_RAGGED
+  // Ragged batches (ragged.hpp; the ragged code object of a run-time model only)
+  RaggedArgs rag;
+  const T* ritems;   // the bound problem's first item
+  __device__ __forceinline__ void set_ragged(const RaggedArgs& a) { rag = a; }
+  __device__ __forceinline__ void bind(long long p) {
+    const RaggedRange r = ragged_range(rag, p);
+    ritems = data + size_t(r.first) * kD;
+    d = static_cast<const T*>(rag.header) + size_t(p) * kH;
+    items = r.count;
+  }
+#else
   __device__ __forceinline__ void bind(long long p) { d = data + size_t(p) * (kH + size_t(items) * kD); }
+#endif
 
   // This lane's share of the pass: its items' cost terms summed into the return value, their gradients into G.
   template <bool WANT_G>
@@ -79,7 +99,11 @@ struct CostModel {
 #pragma unroll
     for (int a = 0; a < kN; ++a) G[a] = T(0);
     T csum = T(0);
+#ifdef TOA_RAGGED
+    const T* itemsp = ritems;
+#else
     const T* itemsp = d + kH;
+#endif
     if constexpr (kN <= 12) {
       T x[kN];
 #pragma unroll
@@ -176,6 +200,11 @@ __global__ void __launch_bounds__(256) gd_fused_kernel(const GdParams* __restric
   const float lr = prm_g->lr;
   Model model;
   model.init(prm_g->items, prm_g->data);
+#ifdef TOA_RAGGED
+  const RaggedArgs& rag = reinterpret_cast<const RaggedGdParams*>(prm_g)->ragged;
+  model.set_ragged(rag);
+  const int* const order = rag.order;   // the q-th problem handed out (null: problem q)
+#endif
   T* X = static_cast<T*>(prm_g->x);
   int* queue = prm_g->queue;
   const int nwaves = int(gridDim.x) * 4;
@@ -190,7 +219,18 @@ __global__ void __launch_bounds__(256) gd_fused_kernel(const GdParams* __restric
       p = __builtin_amdgcn_readfirstlane(p);
     }
     if (p >= P) break;
+#ifdef TOA_RAGGED
+    if (order) p = min(max(order[p], 0), int(P) - 1);   // (wave-uniform: a scalar load; clamped — a slot of a damaged order addresses no problem beyond the batch)
+#endif
     model.bind(p);
+#ifdef TOA_RAGGED
+    if (model.items == 0) {   // no items: kSkipped, x untouched (the LM path's answer to "no residuals", optimizer.h:373-377)
+      lm_init<T>(L, lane);
+      L.st->stop = TOA_STOP_SKIPPED;
+      gd_finalize<T>(L, (long long)p, lane);
+      continue;
+    }
+#endif
     wave_sync();
     L.xs[lane] = lane < n ? X[size_t(p) * n + lane] : T(0);
     wave_sync();
@@ -217,7 +257,7 @@ __global__ void __launch_bounds__(256) gd_fused_kernel(const GdParams* __restric
 // cost [P] = sum_i c_i as accumulated (not normalised, not clamped), nres [P] = 1.
 template <typename Model>
 __global__ void __launch_bounds__(256) cost_accumulate_kernel(const void* data_, const void* x_, long long P, int items, int want_grad,
-                                                              void* g_, double* cost, int* nres, int lds_per_wave) {
+                                                              void* g_, double* cost, int* nres, int lds_per_wave TOA_RAGGED_KARG) {
   using T = typename Model::Scalar;
   constexpr int n = Model::kN;
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -225,6 +265,9 @@ __global__ void __launch_bounds__(256) cost_accumulate_kernel(const void* data_,
   const T* X = static_cast<const T*>(x_);
   Model model;
   model.init(items, data_);
+#ifdef TOA_RAGGED
+  model.set_ragged(rag);
+#endif
   WaveLds<T> L = WaveLds<T>::carve(smem + size_t(wave) * lds_per_wave, 0);
   for (long long p = (long long)blockIdx.x * 4 + wave; p < P; p += (long long)gridDim.x * 4) {
     wave_sync();
@@ -238,7 +281,11 @@ __global__ void __launch_bounds__(256) cost_accumulate_kernel(const void* data_,
     } else {
       model.evaluate(L, lane, c);
     }
+#ifdef TOA_RAGGED
+    if (lane == 0) { cost[p] = double(c); if (nres) nres[p] = model.items > 0 ? 1 : 0; }
+#else
     if (lane == 0) { cost[p] = double(c); if (nres) nres[p] = 1; }
+#endif
   }
 }
 

@@ -3,6 +3,7 @@
 // row_model.hpp (13 <= n <= 63: a row per lane, staged into the MFMA Gram).
 #pragma once
 #include "models_se3.hpp"
+#include "ragged.hpp"
 
 namespace toa {
 
@@ -125,11 +126,26 @@ struct JetModel {
     loss = TOA_LOSS_L2; th2 = T(0); ninl = -1;
   }
   __device__ __forceinline__ void set_loss(int kind, double t2) { loss = kind; th2 = T(t2); }
+#ifdef TOA_RAGGED
+  // Ragged batches (ragged.hpp; the ragged code object of a run-time model only): problem p owns items [off[p], off[p + 1]) of
+  // one concatenated item array and row p of a separate header array.
+  RaggedArgs rag;
+  const T* ritems;   // the bound problem's first item
+  __device__ __forceinline__ void set_ragged(const RaggedArgs& a) { rag = a; }
+  __device__ __forceinline__ void bind(long long p) {
+    const RaggedRange r = ragged_range(rag, p);
+    ritems = data + size_t(r.first) * F::kD;
+    d = static_cast<const T*>(rag.header) + size_t(p) * F::kH;
+    items = r.count;
+    it0 = 0; it1 = r.count;
+  }
+#else
   __device__ __forceinline__ void bind(long long p) {
     const size_t stride = FunctorPackedRows<F>::value ? size_t((items + 3) & ~3) * F::kD : F::kH + size_t(items) * F::kD;
     d = data + size_t(p) * stride;
     it0 = 0; it1 = items;
   }
+#endif
   // rows [row0, row0 + rows) of the problem = whole items (the launchers cut chunks at multiples of kR rows): the row-split form
   __device__ __forceinline__ void bind_chunk(long long p, int row0, int rows, int) {
     bind(p);
@@ -154,7 +170,11 @@ struct JetModel {
     T csum = 0;
     T inl = 0;
     const bool robust = ROBUST && loss != TOA_LOSS_L2;   // wave-uniform
+#ifdef TOA_RAGGED
+    const T* itemsp = ritems;
+#else
     const T* itemsp = d + F::kH;
+#endif
     for (int i = it0 + lane; i < it1; i += 64) {
       const T* item = itemsp + size_t(i) * F::kD;
       if (WANT_H) {

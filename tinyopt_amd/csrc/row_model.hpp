@@ -290,11 +290,28 @@ struct RowModel {
     stage = nullptr;
   }
   __device__ __forceinline__ void set_loss(int kind, double t2) { loss = kind; th2 = T(t2); }
+#ifdef TOA_RAGGED
+  // Ragged batches (ragged.hpp; the ragged code object of a run-time model only): the problem's range from the offsets array, its
+  // header from a separate array; m (and the layout's padded row count) become the bound problem's, as a uniform launch of
+  // that many items would have them.
+  RaggedArgs rag;
+  const T* ritems;   // the bound problem's first item
+  __device__ __forceinline__ void set_ragged(const RaggedArgs& a) { rag = a; }
+  __device__ __forceinline__ void bind(long long p) {
+    const RaggedRange r = ragged_range(rag, p);
+    ritems = data + size_t(r.first) * kD;
+    d = static_cast<const T*>(rag.header) + size_t(p) * F::kH;
+    m = r.count * kR;
+    lay.m4 = (m + 3) & ~3;
+    it0 = 0; it1 = r.count;
+  }
+#else
   __device__ __forceinline__ void bind(long long p) {
     const size_t stride = FunctorPackedRows<F>::value ? lay.elems_per_problem() : F::kH + size_t(m / kR) * kD;
     d = data + size_t(p) * stride;
     it0 = 0; it1 = m / kR;
   }
+#endif
   // row-split execution: rows [r0, r0 + rows) of problem p — r0 on an item boundary (a multiple of lcm(16, kR): jit.hip)
   __device__ __forceinline__ void bind_chunk(long long p, int r0, int rows, int) {
     bind(p);
@@ -406,7 +423,11 @@ struct RowModel {
     const bool robust = ROBUST && loss != TOA_LOSS_L2;   // wave-uniform
     const int nit = it1 - it0;
     const int nss = (nit + IT - 1) / IT;
+#ifdef TOA_RAGGED
+    const T* const items = ritems + size_t(it0) * kD;
+#else
     const T* const items = d + F::kH + size_t(it0) * kD;
+#endif
     const i32x4 rsrc = make_rsrc(items, unsigned(nit) * unsigned(kD) * unsigned(sizeof(T)));
     unsigned char* const stg = static_cast<unsigned char*>(__builtin_assume_aligned(stage, 16));
     const unsigned lds0 = unsigned(reinterpret_cast<size_t>((__attribute__((address_space(3))) unsigned char*)(stg)));

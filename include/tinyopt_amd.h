@@ -668,6 +668,34 @@ int toa_jit_eval_ragged(toa_handle h, toa_jit_model model, const int64_t* item_o
  *      built once, under the #defines of the uniform build that was kept (they fix the stage geometry, hence the bits); it carries a few
  *      registers more than its uniform twin and is NOT re-tried when it spills: look here when a ragged run is slower than expected. */
 int toa_jit_model_stats_ragged(toa_handle h, toa_jit_model m, int* wg_per_cu, int* num_regs, int* scratch_bytes);
+/*      A Gaussian prior beside a run-time model's items: per problem, with n = num_params and in the model's
+ *      scalar type,
+ *        mu_dev  [P][n]
+ *        W_dev   [P][n]      rows = 0, the diagonal form:  r_j = W_j (x_j - mu_j), k = n residuals  (W = 1 / sigma: GaussianPrior)
+ *                [P][k][n]   rows = k in 1 .. n, row-major:  r = W (x - mu)                          (W = U: tests/cov.cpp:96)
+ *      After the item pass of every Build and every cost-only Evaluate: cost += |r|^2, the residual count += k; on a Build also
+ *      g += W^T r and H += W^T W, the diagonal BEFORE damping, clipping and check_min_H_diag — what a hand-written Accumulate
+ *      callback of the reference adds at its end.  The prior's residuals are NOT passed through the handle's M-estimator
+ *      (toa_set_loss) and count as inliers; normalize, final_num_residuals and final_inlier_ratio use the total count;
+ *      final_hessian includes W^T W.  In a ragged batch a problem with no items but a prior is an ordinary problem of k residuals,
+ *      not TOA_STOP_SKIPPED.  Each call mirrors its twin without the prior (the same checks, P == 0 returns TOA_OK, stream-ordered,
+ *      no host read) and always takes the one-launch form (never the row-split).  TOA_E_UNSUPPORTED: a model on TOA_MANIFOLD_SE3 /
+ *      TOA_MANIFOLD_USER (x - mu is not the manifold's minus), a scalar cost model.  TOA_E_ARG: rows < 0 or rows > n, a NULL prior /
+ *      mu_dev / W_dev, pointers of another device.  The kernels are one more code object per model, per form (uniform / ragged) and
+ *      per M-estimator variant, built on first use and cached on disk; that first call is refused under stream capture.
+ *      toa_jit_model_stats_prior: toa_jit_model_stats_ragged of the prior fused kernel (plain L2; ragged != 0: the ragged form). */
+typedef struct toa_prior { const void* mu_dev; const void* W_dev; int32_t rows; int32_t reserved[5]; } toa_prior;   /* rows = 0: diagonal */
+int toa_jit_lm_run_prior(toa_handle h, toa_jit_model model, int num_items, int64_t P, const void* data_dev, void* x_dev, const toa_prior* prior,
+                         const toa_options* options, const toa_results* results, uint64_t* counters_dev);
+int toa_jit_accumulate_prior(toa_handle h, toa_jit_model model, int num_items, int64_t P, const void* data_dev, const void* x_dev,
+                             const toa_prior* prior, int want_grad, void* g_dev, void* H_dev, double* cost_dev, int32_t* nres_dev);
+int toa_jit_lm_run_ragged_prior(toa_handle h, toa_jit_model model, const int64_t* item_offsets_dev, const void* header_dev, int max_items,
+                                int64_t total_items, int64_t P, const void* data_dev, void* x_dev, const toa_prior* prior,
+                                const toa_options* options, const toa_results* results, uint64_t* counters_dev, uint32_t flags);
+int toa_jit_accumulate_ragged_prior(toa_handle h, toa_jit_model model, const int64_t* item_offsets_dev, const void* header_dev, int max_items,
+                                    int64_t total_items, int64_t P, const void* data_dev, const void* x_dev, const toa_prior* prior, int want_grad,
+                                    void* g_dev, void* H_dev, double* cost_dev, int32_t* nres_dev);
+int toa_jit_model_stats_prior(toa_handle h, toa_jit_model m, int ragged, int* wg_per_cu, int* num_regs, int* scratch_bytes);
 
 /* ---- C1: the result gather of a sharded batch (SURVEY §8(b) export list `gather(handle_group...)`, §8(e)).
  *      Problems are independent (the reference optimises exactly one x per call, docs/API.md:12), so a batch of P_total

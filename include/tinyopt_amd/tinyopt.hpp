@@ -366,7 +366,7 @@ class JitResidual {
               int manifold = TOA_MANIFOLD_EUCLID, int kind = TOA_JIT_RESIDUAL, const std::string& plus_body = std::string(), int x_scalars = 0,
               int diff = TOA_DIFF_DEFAULT, float diff_h = 0.f)
       : ctx_(&ctx), n_(n), kR_(residuals_per_item), kD_(item_scalars), kH_(header_scalars),
-        xdim_(manifold == TOA_MANIFOLD_SE3 ? 12 : (manifold == TOA_MANIFOLD_USER ? x_scalars : n)), diff_(diff) {
+        xdim_(manifold == TOA_MANIFOLD_SE3 ? 12 : (manifold == TOA_MANIFOLD_USER ? x_scalars : n)), diff_(diff), manifold_(manifold), kind_(kind) {
     std::vector<char> log(1 << 16);
     toa_jit_spec spec{};
     spec.dtype = dtype_of<Scalar>(); spec.num_params = n; spec.residuals_per_item = residuals_per_item;
@@ -396,6 +396,15 @@ class JitResidual {
   int header_scalars() const { return kH_; }
   int xdim() const { return xdim_; }   // stored scalars of x per problem (12 for an SE3 pose)
   int diff() const { return diff_; }   // TOA_DIFF_*
+  int manifold() const { return manifold_; }   // TOA_MANIFOLD_*
+  int kind() const { return kind_; }           // TOA_JIT_*
+  // stats of the fused kernel with a Gaussian prior (with_prior), uniform or ragged: toa_jit_model_stats_prior
+  struct PriorBuildStats { int wg_per_cu = 0, num_regs = 0, scratch_bytes = 0; };
+  PriorBuildStats stats_prior(bool ragged = false) const {
+    PriorBuildStats s;
+    check(toa_jit_model_stats_prior(ctx_->get(), h_, ragged ? 1 : 0, &s.wg_per_cu, &s.num_regs, &s.scratch_bytes));
+    return s;
+  }
   // What the run-time build came out as (toa_jit_model_stats): resident workgroups per compute unit, LDS per workgroup, vector
   // registers per lane, scratch bytes per lane — a body heavy enough to spill or to drop to one workgroup shows up here.
   struct BuildStats { int wg_per_cu = 0, lds_bytes_per_wg = 0, num_regs = 0, scratch_bytes = 0; };
@@ -408,12 +417,50 @@ class JitResidual {
  private:
   const Context* ctx_;
   toa_jit_model h_ = nullptr;
-  int n_, kR_, kD_, kH_, xdim_, diff_;
+  int n_, kR_, kD_, kH_, xdim_, diff_, manifold_, kind_;
   std::string log_;
 };
+// A Gaussian prior beside a bound run-time model's items (toa_jit_*_prior): per problem r = W (x - mu) after the item pass —
+// cost += |r|^2, g += W^T r, H += W^T W, k more residuals; never robustified.  mu: [P][n] host scalars; W: [P][n] with rows = 0 (the
+// diagonal form, W = 1 / sigma: GaussianPrior) or [P][rows][n] row-major with 1 <= rows <= n (W = U: tests/cov.cpp:96).  Euclidean
+// residual models, the one-launch form only: no host controls, no stepping Optimizer, no diff::Eval / CalculateJac / CheckGradient.
 template <typename Scalar>
-class JitModel : public LossTag {
+class PriorTag {
  public:
+  bool has_prior() const { return prior_rows_ >= 0; }
+  toa_prior prior_pod() const {
+    toa_prior p{};
+    p.mu_dev = prior_mu_.data(); p.W_dev = prior_W_.data(); p.rows = prior_rows_;
+    return p;
+  }
+
+ protected:
+  void set_prior(const JitResidual<Scalar>& res, int64_t P, const Scalar* mu, const Scalar* W, int rows) {
+    if (res.kind() == TOA_JIT_COST || res.kind() == TOA_JIT_COST_GRAD)
+      throw std::invalid_argument("tinyopt_amd::with_prior: a scalar cost model has no residuals to add a Gaussian prior to");
+    if (res.manifold() != TOA_MANIFOLD_EUCLID)
+      throw std::invalid_argument("tinyopt_amd::with_prior: x - mu is not the manifold's minus: Euclidean parameters only");
+    if (rows < 0 || rows > res.n()) throw std::invalid_argument("tinyopt_amd::with_prior: rows must be 0 (diagonal) or 1 .. n");
+    if (!mu || !W) throw std::invalid_argument("tinyopt_amd::with_prior: mu / W must not be null");
+    const size_t n = size_t(res.n()), per = rows ? size_t(rows) * n : n;
+    prior_mu_ = DeviceBuffer<Scalar>(res.ctx(), std::max<size_t>(1, size_t(P) * n));
+    prior_W_ = DeviceBuffer<Scalar>(res.ctx(), std::max<size_t>(1, size_t(P) * per));
+    if (P > 0) {
+      check(toa_memcpy_h2d(res.ctx().get(), prior_mu_.data(), mu, size_t(P) * n * sizeof(Scalar)));
+      check(toa_memcpy_h2d(res.ctx().get(), prior_W_.data(), W, size_t(P) * per * sizeof(Scalar)));
+    }
+    prior_rows_ = rows;
+  }
+
+ private:
+  DeviceBuffer<Scalar> prior_mu_, prior_W_;
+  int prior_rows_ = -1;   // -1: no prior
+};
+template <typename Scalar>
+class JitModel : public LossTag, public PriorTag<Scalar> {
+ public:
+  JitModel& with_prior(const Scalar* mu, const Scalar* W, int rows = 0) & { this->set_prior(*res_, P_, mu, W, rows); return *this; }
+  JitModel&& with_prior(const Scalar* mu, const Scalar* W, int rows = 0) && { this->set_prior(*res_, P_, mu, W, rows); return std::move(*this); }
   JitModel(const JitResidual<Scalar>& res, int64_t P, int items, const Scalar* host)
       : res_(&res), P_(P), items_(items), data_(res.ctx(), size_t(P) * (res.header_scalars() + size_t(items) * res.item_scalars())) {
     data_.upload(host);
@@ -439,8 +486,10 @@ class JitModel : public LossTag {
 // and diff::CalculateJac, whose outputs are concatenated like the items.  One-launch form only: no host controls (stop callbacks,
 // max_duration_ms, the log line), no stepping Optimizer, no diff::CheckGradient.
 template <typename Scalar>
-class RaggedJitModel : public LossTag {
+class RaggedJitModel : public LossTag, public PriorTag<Scalar> {
  public:
+  RaggedJitModel& with_prior(const Scalar* mu, const Scalar* W, int rows = 0) & { this->set_prior(*res_, P_, mu, W, rows); return *this; }
+  RaggedJitModel&& with_prior(const Scalar* mu, const Scalar* W, int rows = 0) && { this->set_prior(*res_, P_, mu, W, rows); return std::move(*this); }
   RaggedJitModel(const JitResidual<Scalar>& res, const std::vector<int64_t>& counts, const Scalar* host, const Scalar* header)
       : res_(&res), P_(int64_t(counts.size())), offsets_host_(counts.size() + 1, 0) {
     for (size_t p = 0; p < counts.size(); ++p) {
@@ -487,6 +536,16 @@ template <typename C, typename = void> struct is_ragged : std::false_type {};
 template <typename C> struct is_ragged<C, std::void_t<decltype(std::declval<const C&>().ragged_handle())>> : std::true_type {};
 template <typename C, typename = void> struct is_jit : std::false_type {};
 template <typename C> struct is_jit<C, std::void_t<decltype(std::declval<const C&>().jit_handle())>> : std::true_type {};
+template <typename C, typename = void> struct takes_prior : std::false_type {};
+template <typename C> struct takes_prior<C, std::void_t<decltype(std::declval<const C&>().has_prior())>> : std::true_type {};
+template <typename C>
+inline bool has_prior(const C& cost) {
+  if constexpr (takes_prior<C>::value) return cost.has_prior();
+  else return false;
+}
+inline void refuse_prior(const char* what) {
+  throw std::invalid_argument(std::string("tinyopt_amd: a Gaussian prior (with_prior) stands beside a Euclidean residual model in the one-launch form only: ") + what);
+}
 }  // namespace detail
 
 // include/tinyopt/output.h:26-145, one entry per problem.
@@ -542,6 +601,10 @@ BatchOutput Optimize(std::vector<Scalar>& x, const Cost& cost, const Options& op
       throw std::invalid_argument("tinyopt_amd::Optimize: a numerically differentiated model runs as one launch per solve: stop callbacks, "
                                   "max_duration_ms and the log line are not supported (it has no stepping form)");
   }
+  if (detail::has_prior(cost)) {
+    if (options.has_host_controls()) detail::refuse_prior("no stepping form, so no host controls (stop callbacks, max_duration_ms, the log line)");
+    if (gd) detail::refuse_prior("no GradientDescent");
+  }
   if constexpr (detail::is_ragged<Cost>::value) {
     if (options.has_host_controls())
       throw std::invalid_argument("tinyopt_amd::Optimize: a ragged batch (bind_ragged) runs in the one-launch form only: no stepping form, so "
@@ -583,6 +646,10 @@ BatchOutput Optimize(std::vector<Scalar>& x, const Cost& cost, const Options& op
       const toa_gd_options gpod = options.gd_pod();
       check(toa_jit_gd_run_ragged(ctx.get(), cost.ragged_handle(), cost.offsets_dev(), cost.header(), cost.max_items(), cost.total_items(), P,
                                   cost.data(), dx.data(), &pod, &gpod, &r, nullptr, flags));
+    } else if (cost.has_prior()) {
+      const toa_prior pr = cost.prior_pod();
+      check(toa_jit_lm_run_ragged_prior(ctx.get(), cost.ragged_handle(), cost.offsets_dev(), cost.header(), cost.max_items(), cost.total_items(), P,
+                                        cost.data(), dx.data(), &pr, &pod, &r, nullptr, flags));
     } else {
       check(toa_jit_lm_run_ragged(ctx.get(), cost.ragged_handle(), cost.offsets_dev(), cost.header(), cost.max_items(), cost.total_items(), P,
                                   cost.data(), dx.data(), &pod, &r, nullptr, flags));
@@ -591,6 +658,9 @@ BatchOutput Optimize(std::vector<Scalar>& x, const Cost& cost, const Options& op
     if (gd) {   // gd::Optimizer on a scalar cost model (the library refuses any other model: optimize.h:59-75)
       const toa_gd_options gpod = options.gd_pod();
       check(toa_jit_gd_run(ctx.get(), cost.jit_handle(), cost.items(), P, cost.data(), dx.data(), &pod, &gpod, &r, nullptr));
+    } else if (cost.has_prior()) {
+      const toa_prior pr = cost.prior_pod();
+      check(toa_jit_lm_run_prior(ctx.get(), cost.jit_handle(), cost.items(), P, cost.data(), dx.data(), &pr, &pod, &r, nullptr));
     } else {
       check(toa_jit_lm_run(ctx.get(), cost.jit_handle(), cost.items(), P, cost.data(), dx.data(), &pod, &r, nullptr));
     }
@@ -623,6 +693,7 @@ GradientCheck CheckGradient(const JitModel<Scalar>& model, const std::vector<Sca
   const int64_t P = model.P();
   if (int64_t(x.size()) != P * model.xdim())
     throw std::invalid_argument("tinyopt_amd::diff::CheckGradient: x must hold P * (parameters per problem) scalars");
+  if (model.has_prior()) detail::refuse_prior("no CheckGradient (it checks the model's own rows)");
   const Context& ctx = model.ctx();
   DeviceBuffer<Scalar> dx(ctx, x.size());
   dx.upload(x.data());
@@ -656,6 +727,7 @@ std::pair<std::vector<Scalar>, std::vector<Scalar>> Eval(const JitModel<Scalar>&
   const int64_t P = model.P();
   if (int64_t(x.size()) != P * model.xdim())
     throw std::invalid_argument("tinyopt_amd::diff::Eval: x must hold P * (parameters per problem) scalars");
+  if (model.has_prior()) detail::refuse_prior("no Eval / CalculateJac (they return the model's own rows)");
   const Context& ctx = model.ctx();
   const size_t rows = size_t(P) * size_t(model.m());
   DeviceBuffer<Scalar> dx(ctx, x.size());
@@ -676,6 +748,7 @@ std::vector<Scalar> CalculateJac(const JitModel<Scalar>& model, const std::vecto
   const int64_t P = model.P();
   if (int64_t(x.size()) != P * model.xdim())
     throw std::invalid_argument("tinyopt_amd::diff::CalculateJac: x must hold P * (parameters per problem) scalars");
+  if (model.has_prior()) detail::refuse_prior("no Eval / CalculateJac (they return the model's own rows)");
   const Context& ctx = model.ctx();
   const size_t elems = size_t(P) * size_t(model.m()) * size_t(model.n());
   DeviceBuffer<Scalar> dx(ctx, x.size());
@@ -694,6 +767,7 @@ std::pair<std::vector<Scalar>, std::vector<Scalar>> Eval(const RaggedJitModel<Sc
   const int64_t P = model.P();
   if (int64_t(x.size()) != P * model.xdim())
     throw std::invalid_argument("tinyopt_amd::diff::Eval: x must hold P * (parameters per problem) scalars");
+  if (model.has_prior()) detail::refuse_prior("no Eval / CalculateJac (they return the model's own rows)");
   const Context& ctx = model.ctx();
   const size_t rows = size_t(model.rows());
   DeviceBuffer<Scalar> dx(ctx, std::max<size_t>(1, x.size()));
@@ -730,6 +804,7 @@ class Optimizer {
         state_(cost.ctx(), toa_lm_state_bytes(dtype_of<Scalar>(), n_, P_)) {
     if (int64_t(x.size()) != P_ * cost.xdim())
       throw std::invalid_argument("tinyopt_amd::Optimizer: x must hold P * (parameters per problem) scalars");
+    if (detail::has_prior(cost)) detail::refuse_prior("no stepping form (Optimizer)");
     dx_.upload(x.data());
     stop_.zero(); iters_.zero(); fc_.zero();
     r_ = toa_results{};

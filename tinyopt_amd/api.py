@@ -281,6 +281,61 @@ class _LossMixin:
         return m
 
 
+class _PriorMixin:
+    """Bound run-time models that take a Gaussian prior beside their items: ``model.with_prior(mu, W)`` — per problem
+    ``r = W (x - mu)`` appended to the items' residuals after every pass (cost += |r|^2, g += W^T r, H += W^T W, k more
+    residuals), what a hand-written Accumulate callback of the reference adds at its end.  ``mu``: [P, n].  ``W``: [P, n] is the
+    diagonal form (``W = 1 / sigma``: the reference's GaussianPrior, k = n), [P, k, n] with 1 <= k <= n the full form (``W = U``:
+    MahaPrior, tests/cov.cpp:96).  The prior is never passed through ``with_loss``'s M-estimator and its residuals count as inliers;
+    ``Output.Covariance()`` of a prior'd run is the posterior covariance.  Composes with ``with_loss``.  Euclidean residual models
+    only; no ``splits`` (and never the automatic row-split), no host controls, no ``Optimizer``, no ``Eval`` / ``CalculateJac`` /
+    ``CheckGradient`` (those are about the model's own rows)."""
+    prior = None   # (mu, W, rows): rows = 0 the diagonal form
+
+    def with_prior(self, mu: torch.Tensor, W: torch.Tensor):
+        import copy
+        res = self.res
+        if res.kind in JitResidual.COST_KINDS:
+            _refuse_prior('a scalar cost model (kind="cost" / "cost_grad", GradientDescent) has no residuals to add a prior to')
+        if res.manifold != "euclid":
+            _refuse_prior(f'manifold={res.manifold!r}: x - mu is not the manifold\'s minus (Euclidean parameters only)')
+        if not isinstance(mu, torch.Tensor) or not isinstance(W, torch.Tensor):
+            raise ValueError("with_prior: mu and W must be tensors")
+        P, n = self.P, self.n
+        if tuple(mu.shape) != (P, n):
+            raise ValueError(f"with_prior: mu must be [P, n] = [{P}, {n}], not {list(mu.shape)}")
+        if W.dim() == 2:
+            if tuple(W.shape) != (P, n):
+                raise ValueError(f"with_prior: a diagonal W must be [P, n] = [{P}, {n}], not {list(W.shape)}")
+            rows = 0
+        elif W.dim() == 3:
+            if W.shape[0] != P or W.shape[2] != n:
+                raise ValueError(f"with_prior: a full W must be [P, k, n] = [{P}, k, {n}], not {list(W.shape)}")
+            rows = int(W.shape[1])
+            if rows < 1 or rows > n:
+                raise ValueError(f"with_prior: a full W has 1 <= k <= n = {n} rows, not {rows}")
+        else:
+            raise ValueError(f"with_prior: W must be [P, n] (diagonal) or [P, k, n] (full), not {W.dim()}-dimensional")
+        for name, t in (("mu", mu), ("W", W)):
+            if t.dtype != self.dtype:
+                raise ValueError(f"with_prior: {name} must have the model's dtype {self.dtype}, not {t.dtype}")
+            if t.device != self._prior_device():
+                raise ValueError(f"with_prior: {name} must be on the model's device {self._prior_device()}, not {t.device}")
+        m = copy.copy(self)          # shares the device data
+        m.prior = (mu.contiguous(), W.contiguous(), rows)
+        return m
+
+    def _prior_pod(self):
+        from ._capi import ToaPrior
+        pod = ToaPrior()
+        pod.mu_dev, pod.W_dev, pod.rows = self.prior[0].data_ptr(), self.prior[1].data_ptr(), self.prior[2]
+        return pod
+
+
+def _refuse_prior(what: str):
+    raise ValueError(f"a Gaussian prior (with_prior) stands beside a Euclidean residual model in the one-launch form only: {what}")
+
+
 def _apply_loss(ctx: "Context", cost) -> None:
     """The handle carries the cost functor's M-estimator (toa_set_loss): set it from the model before every launch."""
     # SE3Reproj carries its loss in the data header: a model without one runs the kernels without the M-estimator branch (toa_tuning::
@@ -570,6 +625,13 @@ class JitResidual:
         header: [P, header_scalars].  A count of 0 is legal (that problem ends with kSkipped, x untouched)."""
         return RaggedJitModel(self, data, counts, offsets, header)
 
+    def stats_prior(self, ragged: bool = False) -> dict:
+        """``stats_ragged`` of the fused kernel with a Gaussian prior (``with_prior``), uniform or ragged (its plain L2 build,
+        compiled by this call if it was not yet)."""
+        v = [C.c_int(0) for _ in range(3)]
+        check(self.ctx.lib.toa_jit_model_stats_prior(self.ctx.h, self._h, int(bool(ragged)), *[C.byref(t) for t in v]))
+        return dict(wg_per_cu=v[0].value, num_regs=v[1].value, scratch_bytes=v[2].value)
+
     def stats_ragged(self) -> dict:
         """``stats`` of the ragged fused kernel (its plain L2 build, compiled by this call if it was not yet)."""
         v = [C.c_int(0) for _ in range(3)]
@@ -588,7 +650,7 @@ class JitResidual:
             pass
 
 
-class JitModel(_LossMixin):
+class JitModel(_LossMixin, _PriorMixin):
     """A JitResidual bound to its problem data ([P][header | items x item_scalars], the layout of the built-in Jet families)."""
     model_id = None
 
@@ -606,6 +668,9 @@ class JitModel(_LossMixin):
             assert header is not None and header.shape == (self.P, res.kH) and header.dtype == res.dtype
             flat = torch.cat([header, flat], dim=1)
         self.packed = flat.contiguous()
+
+    def _prior_device(self):
+        return self.packed.device
 
     @property
     def algorithmic_bytes_per_pass(self) -> int:
@@ -641,7 +706,7 @@ def ragged_offsets(counts=None, offsets=None, total_items: Optional[int] = None)
     return off
 
 
-class RaggedJitModel(_LossMixin):
+class RaggedJitModel(_LossMixin, _PriorMixin):
     """A JitResidual bound to a RAGGED batch: data [total_items, item_scalars] (the items of all problems, one after another), a
     separate header [P, header_scalars] and int64 offsets [P + 1].  Taken by ``Optimize`` (LM, GN; GradientDescent for cost kinds),
     ``accumulate``, ``Eval`` and ``CalculateJac``; every problem computes bit for bit what it would alone in a uniform batch of
@@ -681,6 +746,9 @@ class RaggedJitModel(_LossMixin):
         if not self.P:
             return 0.0
         return (self.total_items * self.res.kD / self.P + self.res.kH) * self.data.element_size()
+
+    def _prior_device(self):
+        return self.data.device
 
     def _ragged_args(self):
         return (self.offsets.data_ptr(), self.header.data_ptr() if self.header is not None else None, self.max_items, self.total_items)
@@ -971,6 +1039,24 @@ def Optimize(x: torch.Tensor, cost, options: Optional[Options] = None, *, histor
                                        cost.obs_cam.data_ptr(), cost.obs_pt.data_ptr(), cost.obs_uv.data_ptr(), x.data_ptr(),
                                        C.byref(pod), C.byref(res), out.counters.data_ptr(), float(options.max_duration_ms or 0.0)))
         return out
+    if isinstance(cost, JitModel) and cost.prior is not None:
+        if splits is not None:
+            _refuse_prior("no row-split form (splits)")
+        if options.has_host_controls():
+            _refuse_prior("no stepping form, so no host controls (stop callbacks, max_duration_ms, the log line)")
+        if options.solver_type == Options.GradientDescent:
+            _refuse_prior("no GradientDescent")
+        pod = options.to_pod()
+        if out is None:
+            out = _alloc_output(P, n, options, history, x.device)
+        elif zero_counters:
+            out.counters.zero_()
+        res = _results_pod(out)
+        _apply_loss(ctx, cost)
+        pr = cost._prior_pod()
+        check(ctx.lib.toa_jit_lm_run_prior(ctx.h, cost.res._h, cost.items, P, cost.packed.data_ptr(), x.data_ptr(), C.byref(pr), C.byref(pod),
+                                           C.byref(res), out.counters.data_ptr()))
+        return out
     if isinstance(cost, JitModel) and cost.res.diff != "ad" and (options.has_host_controls() or splits is not None):
         raise ValueError("a numerically differentiated model (diff=...) runs as one launch per solve: no stop callbacks, max_duration_ms, "
                          "log line or splits (it has no stepping and no row-split form)")
@@ -1051,6 +1137,8 @@ def _optimize_ragged(x: torch.Tensor, cost: "RaggedJitModel", options: Options, 
         _refuse_ragged("no row-split form (splits)")
     if options.has_host_controls():
         _refuse_ragged("no stepping form, so no host controls (stop callbacks, max_duration_ms, the log line)")
+    if cost.prior is not None and options.solver_type == Options.GradientDescent:
+        _refuse_prior("no GradientDescent")
     P = x.shape[0]
     gd_run = cost.res.kind in JitResidual.COST_KINDS and options.solver_type == Options.GradientDescent
     pod = options.to_pod()
@@ -1074,6 +1162,10 @@ def _optimize_ragged(x: torch.Tensor, cost: "RaggedJitModel", options: Options, 
         res.final_hessian = None
         check(ctx.lib.toa_jit_gd_run_ragged(ctx.h, cost.res._h, *cost._ragged_args(), P, cost.data.data_ptr(), x.data_ptr(), C.byref(pod),
                                             C.byref(gd), C.byref(res), out.counters.data_ptr(), flags))
+    elif cost.prior is not None:
+        pr = cost._prior_pod()
+        check(ctx.lib.toa_jit_lm_run_ragged_prior(ctx.h, cost.res._h, *cost._ragged_args(), P, cost.data.data_ptr(), x.data_ptr(), C.byref(pr),
+                                                  C.byref(pod), C.byref(res), out.counters.data_ptr(), flags))
     else:
         check(ctx.lib.toa_jit_lm_run_ragged(ctx.h, cost.res._h, *cost._ragged_args(), P, cost.data.data_ptr(), x.data_ptr(), C.byref(pod),
                                             C.byref(res), out.counters.data_ptr(), flags))
@@ -1092,6 +1184,8 @@ class Optimizer:
         _check_call(x, cost)
         if isinstance(cost, RaggedJitModel):
             _refuse_ragged("no stepping form (Optimizer)")
+        if getattr(cost, "prior", None) is not None:
+            _refuse_prior("no stepping form (Optimizer)")
         if isinstance(cost, JitModel) and cost.res.diff != "ad":
             raise ValueError("a numerically differentiated model (diff=...) has no stepping form")
         self.x, self.cost = x, cost
@@ -1292,6 +1386,16 @@ def accumulate(cost, x: torch.Tensor, want_grad: bool = True, ctx: Optional[Cont
     c = torch.zeros(P, dtype=torch.float64, device=dev)
     nres = torch.zeros(P, dtype=torch.int32, device=dev)
     _apply_loss(ctx, cost)
+    if getattr(cost, "prior", None) is not None:   # (never a cost kind: with_prior refuses those)
+        pr = cost._prior_pod()
+        gp, Hp = (g.data_ptr(), H.data_ptr()) if want_grad else (None, None)
+        if isinstance(cost, RaggedJitModel):
+            check(ctx.lib.toa_jit_accumulate_ragged_prior(ctx.h, cost.res._h, *cost._ragged_args(), P, cost.data.data_ptr(), x.data_ptr(), C.byref(pr),
+                                                          int(want_grad), gp, Hp, c.data_ptr(), nres.data_ptr()))
+        else:
+            check(ctx.lib.toa_jit_accumulate_prior(ctx.h, cost.res._h, cost.items, P, cost.packed.data_ptr(), x.data_ptr(), C.byref(pr),
+                                                   int(want_grad), gp, Hp, c.data_ptr(), nres.data_ptr()))
+        return g, H, c, nres
     if isinstance(cost, RaggedJitModel):   # (a problem without items: zeros, nres = 0)
         is_cost = cost.res.kind in JitResidual.COST_KINDS
         check(ctx.lib.toa_jit_accumulate_ragged(ctx.h, cost.res._h, *cost._ragged_args(), P, cost.data.data_ptr(), x.data_ptr(), int(want_grad),
@@ -1332,6 +1436,8 @@ def CheckGradient(model: "JitModel", x: torch.Tensor, eps: Optional[float] = Non
     x [P, n]: the model's own derivatives against finite differences of its residuals (or cost terms) with step eps / 10.
     Residual kinds compare g = J^T r and, with ``check_H``, H = J^T J; cost kinds compare g.  ``eps`` None: the reference's default
     (1e-2 in float32, 1e-5 in float64).  The first check of a model with a (method, eps) compiles its numeric twin (then cached)."""
+    if getattr(model, "prior", None) is not None:
+        _refuse_prior("no CheckGradient (it checks the model's own rows: check the model without the prior)")
     if isinstance(model, RaggedJitModel):
         _refuse_ragged("no CheckGradient (check the model on a uniform batch: JitResidual.bind)")
     if not isinstance(model, JitModel):
@@ -1369,6 +1475,8 @@ def Eval(model: "JitModel", x: torch.Tensor, jac: bool = True, ctx: Optional[Con
     Not for scalar costs (``accumulate`` already returns their value and gradient) and not with a loss set.  ``res_out`` /
     ``J_out``: write into the caller's tensors (views are fine as long as they are contiguous).  The first call of a model
     compiles its Eval kernels (then cached)."""
+    if getattr(model, "prior", None) is not None:
+        _refuse_prior("no Eval (it returns the model's own rows: evaluate the model without the prior)")
     if isinstance(model, RaggedJitModel):   # outputs concatenated like the items: res [rows], J [rows, n]
         _check_call(x, model)
         ctx = ctx or default_context(x.device.index)
@@ -1393,6 +1501,8 @@ def Eval(model: "JitModel", x: torch.Tensor, jac: bool = True, ctx: Optional[Con
 
 def CalculateJac(model: "JitModel", x: torch.Tensor, ctx: Optional[Context] = None, *, J_out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """``diff::CalculateJac(x, f)`` (diff/auto_diff.h:120-138): the Jacobian rows J [P, m, n] alone (see ``Eval``)."""
+    if getattr(model, "prior", None) is not None:
+        _refuse_prior("no CalculateJac (it returns the model's own rows: evaluate the model without the prior)")
     if isinstance(model, RaggedJitModel):
         _check_call(x, model)
         ctx = ctx or default_context(x.device.index)

@@ -2,6 +2,7 @@
 // queue, memo, cooperative tail) and the seams accumulate_kernel (K1 / K2), solve_damped_kernel (K3), inv_cov_kernel.
 #pragma once
 #include "models_jet.hpp"
+#include "prior.hpp"
 
 namespace toa {
 
@@ -67,6 +68,13 @@ struct FusedParams {
 struct RaggedFusedParams {
   FusedParams f;
   RaggedArgs ragged;
+};
+// ... and of a launch with a Gaussian prior (prior.hpp), uniform or ragged: the ragged block, then the prior's arguments (a
+// uniform launch leaves `ragged` zero).  Only a code object built with TOA_PRIOR reads that far.
+struct PriorFusedParams {
+  FusedParams f;
+  RaggedArgs ragged;
+  PriorArgs prior;
 };
 
 template <typename M, typename = void>
@@ -144,6 +152,9 @@ __global__ void __launch_bounds__(64 * ModelWaves<Model>::value) TOA_FUSED_ATTR 
   const RaggedArgs& rag = reinterpret_cast<const RaggedFusedParams*>(prm_g)->ragged;
   model.set_ragged(rag);
   const int* const order = rag.order;   // the q-th problem handed out (null: problem q)
+#endif
+#ifdef TOA_PRIOR
+  model.set_prior(reinterpret_cast<const PriorFusedParams*>(prm_g)->prior, L.M, L.LD);
 #endif
   if constexpr (ModelStageBytes<Model>::value > 0) model.stage = reinterpret_cast<unsigned char*>(smem) + size_t(wave) * prm_g->lds_per_wave + prm_g->stage_off;
   T* X = static_cast<T*>(prm_g->x);
@@ -250,7 +261,7 @@ __global__ void __launch_bounds__(64 * ModelWaves<Model>::value) TOA_FUSED_ATTR 
 template <typename Model>
 __global__ void __launch_bounds__(256) accumulate_kernel(const void* data_, const void* x_, long long P, int n, int m,
                                                          int want_grad, void* g_, void* H_, double* cost, int* nres,
-                                                         int lds_per_wave, int loss, double loss_th2 TOA_RAGGED_KARG) {
+                                                         int lds_per_wave, int loss, double loss_th2 TOA_RAGGED_KARG TOA_PRIOR_KARG) {
   using T = typename Model::Scalar;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -262,6 +273,9 @@ __global__ void __launch_bounds__(256) accumulate_kernel(const void* data_, cons
   model.set_ragged(rag);
 #endif
   WaveLds<T> L = WaveLds<T>::carve(model_bind_stage(model, smem + size_t(wave) * lds_per_wave, n), n);
+#ifdef TOA_PRIOR
+  model.set_prior(pri, L.M, L.LD);
+#endif
   const int xd = Model::kXdim ? Model::kXdim : n;
   for (long long p = (long long)blockIdx.x * 4 + wave; p < P; p += (long long)gridDim.x * 4) {
     wave_sync();

@@ -5,7 +5,7 @@
 //   offsets  int64 [P + 1]       non-decreasing, [0] = 0, [P] = total_items: problem p owns items [off[p], off[p + 1])
 //
 // The ragged kernels are the uniform ones compiled with TOA_RAGGED defined (a code object of their own, jit.hip
-// ensure_ragged): the models' bind(p) then takes the problem's range from `offsets`, and the persistent kernels walk an
+// ensure_form): the models' bind(p) then takes the problem's range from `offsets`, and the persistent kernels walk an
 // `order[P]` array (longest problems first) instead of the problem index.  Nothing here is seen by a build without the macro
 // except the plain structs below.
 #pragma once

@@ -168,7 +168,8 @@ int toa_create(toa_handle* out, int device, void* stream);
  *      The host mirrors (include/tinyopt_amd/tinyopt.hpp, tinyopt_amd/_capi.py) refuse a library whose version differs. */
 #define TOA_ABI_VERSION 7   /* 7: toa_gd_options, toa_jit_gd_run, TOA_JIT_COST / TOA_JIT_COST_GRAD */
 /* Added under version 7 (additive: new functions, and fields carved out of words every caller already zeroes):
- *   toa_jit_spec::diff / diff_h (the first two words of what was reserved[6]), TOA_DIFF_*, toa_jit_check_gradient. */
+ *   toa_jit_spec::diff / diff_h (the first two words of what was reserved[6]), TOA_DIFF_*, toa_jit_check_gradient.
+ *   toa_jit_spec::large_n (the first word of what was reserved[4]): run-time models of up to 1024 parameters on the launch-per-phase route. */
 int toa_abi_version(void);
 
 /* ---- tuning (per handle).  The arms of the A/B logs (profiles/r0N_ab_log.md) and of the bit-identity tests, as typed state
@@ -550,7 +551,15 @@ typedef struct toa_jit_spec {
   const char* plus_body;   /* TOA_MANIFOLD_USER: the body of `template <class S> void plus(const T* x, const S* d, S* xp)`: xp = x (+) d */
   int32_t diff;       /* TOA_DIFF_*: how the body is differentiated (0 = as before: Jets, or the body's own derivatives) */
   float diff_h;       /* TOA_DIFF_NUM_*: the step h; 0 = FloatEpsilon<T> (1e-4f / 1e-7f, math.h:298-301) */
-  int32_t reserved[4];   /* (diff and diff_h were reserved[0..1]: the size and every other offset are what they were) */
+  union {
+    int32_t reserved[4];   /* (diff and diff_h were reserved[0..1]: the size and every other offset are what they were) */
+    int32_t large_n;  /* = reserved[0].  0 = the one-wavefront routes (num_params <= 63).  1 = compile the model for the launch-per-phase
+                         pipeline of the wide problems (rows kernel, Gram on the matrix cores, this library's LDL^T / blocked Cholesky):
+                         TOA_JIT_RESIDUAL / TOA_JIT_ACCUMULATE, Euclidean parameters, diff = TOA_DIFF_DEFAULT, 1 <= num_params <= 1024 in
+                         fp32 / 512 in fp64, scalars_per_item <= 2048.  Such a model is taken by toa_jit_lm_run (LM / GN, no M-estimator, not
+                         under stream capture), toa_jit_accumulate and toa_jit_eval; every other toa_jit_* entry refuses it with
+                         TOA_E_UNSUPPORTED.  toa_jit_model_stats describes its rows kernel.  reserved[1..3] stay zero. */
+  };
 } toa_jit_spec;
 int toa_model_compile_ex(toa_handle h, const toa_jit_spec* spec, const char* body, toa_jit_model* out, char* log_out, size_t log_cap);
 int toa_jit_set_cache_dir(const char* dir);

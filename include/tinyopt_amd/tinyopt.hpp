@@ -362,17 +362,22 @@ class JitResidual {
   // diff: TOA_DIFF_DEFAULT (Jets, or the body's own derivatives), or TOA_DIFF_NUM_* (diff::to_pod(diff::kCentral) ...) — a TOA_JIT_RESIDUAL /
   //   TOA_JIT_COST body differentiated by finite differences with step diff_h (0 = FloatEpsilon<Scalar>), CreateNumDiffFunc1 / 2 of
   //   diff/num_diff.h: the body runs on plain Scalar only.  Euclidean; no stop callbacks / max_duration_ms / log line.
+  // large_n = true: the model is compiled for the launch-per-phase pipeline of the wide problems instead of a wavefront per problem —
+  //   n up to 1024 (float) / 512 (double), item_scalars up to 2048; TOA_JIT_RESIDUAL / TOA_JIT_ACCUMULATE, Euclidean, TOA_DIFF_DEFAULT.
+  //   Optimize (LM / GN), Accumulate and diff::Eval / CalculateJac take it; with_loss, with_prior, bind_ragged, splits, the stepping
+  //   Optimizer, host controls, GradientDescent and diff::CheckGradient are refused (std::invalid_argument).  Without it n = 64 is refused.
   JitResidual(const Context& ctx, const std::string& body, int n, int item_scalars, int residuals_per_item = 1, int header_scalars = 0,
               int manifold = TOA_MANIFOLD_EUCLID, int kind = TOA_JIT_RESIDUAL, const std::string& plus_body = std::string(), int x_scalars = 0,
-              int diff = TOA_DIFF_DEFAULT, float diff_h = 0.f)
+              int diff = TOA_DIFF_DEFAULT, float diff_h = 0.f, bool large_n = false)
       : ctx_(&ctx), n_(n), kR_(residuals_per_item), kD_(item_scalars), kH_(header_scalars),
-        xdim_(manifold == TOA_MANIFOLD_SE3 ? 12 : (manifold == TOA_MANIFOLD_USER ? x_scalars : n)), diff_(diff), manifold_(manifold), kind_(kind) {
+        xdim_(manifold == TOA_MANIFOLD_SE3 ? 12 : (manifold == TOA_MANIFOLD_USER ? x_scalars : n)), diff_(diff), manifold_(manifold), kind_(kind), large_n_(large_n) {
     std::vector<char> log(1 << 16);
     toa_jit_spec spec{};
     spec.dtype = dtype_of<Scalar>(); spec.num_params = n; spec.residuals_per_item = residuals_per_item;
     spec.scalars_per_item = item_scalars; spec.header_scalars = header_scalars; spec.manifold = manifold; spec.kind = kind;
     if (manifold == TOA_MANIFOLD_USER) { spec.x_scalars = x_scalars; spec.plus_body = plus_body.c_str(); }
     spec.diff = diff; spec.diff_h = diff_h;
+    spec.large_n = large_n ? 1 : 0;
     const int rc = toa_model_compile_ex(ctx.get(), &spec, body.c_str(), &h_, log.data(), log.size());
     log_ = log.data();
     check(rc);
@@ -398,6 +403,7 @@ class JitResidual {
   int diff() const { return diff_; }   // TOA_DIFF_*
   int manifold() const { return manifold_; }   // TOA_MANIFOLD_*
   int kind() const { return kind_; }           // TOA_JIT_*
+  bool large_n() const { return large_n_; }    // compiled for the launch-per-phase pipeline (up to 1024 / 512 parameters)
   // stats of the fused kernel with a Gaussian prior (with_prior), uniform or ragged: toa_jit_model_stats_prior
   struct PriorBuildStats { int wg_per_cu = 0, num_regs = 0, scratch_bytes = 0; };
   PriorBuildStats stats_prior(bool ragged = false) const {
@@ -418,6 +424,7 @@ class JitResidual {
   const Context* ctx_;
   toa_jit_model h_ = nullptr;
   int n_, kR_, kD_, kH_, xdim_, diff_, manifold_, kind_;
+  bool large_n_;
   std::string log_;
 };
 // A Gaussian prior beside a bound run-time model's items (toa_jit_*_prior): per problem r = W (x - mu) after the item pass —

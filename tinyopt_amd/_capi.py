@@ -68,10 +68,15 @@ class ToaTuning(C.Structure):   # include/tinyopt_amd.h toa_tuning
                                          "large_library_gram", "large_library_solver", "fail_workspace_alloc", "large_one_lane", "large_chol_no_lookahead", "large_gram_plain_deal", "narrow_mfma_pass", "se3_reproj_header_l2")] + [("reserved", C.c_int32 * 13)]
 
 
+class _ToaJitSpecTail(C.Union):   # toa_jit_spec's last four words: large_n is reserved[0]
+    _fields_ = [("reserved", C.c_int32 * 4), ("large_n", C.c_int32)]
+
+
 class ToaJitSpec(C.Structure):   # include/tinyopt_amd.h toa_jit_spec
+    _anonymous_ = ("_tail",)
     _fields_ = [("dtype", C.c_int32), ("num_params", C.c_int32), ("residuals_per_item", C.c_int32), ("scalars_per_item", C.c_int32),
                 ("header_scalars", C.c_int32), ("manifold", C.c_int32), ("kind", C.c_int32), ("x_scalars", C.c_int32),
-                ("plus_body", C.c_char_p), ("diff", C.c_int32), ("diff_h", C.c_float), ("reserved", C.c_int32 * 4)]
+                ("plus_body", C.c_char_p), ("diff", C.c_int32), ("diff_h", C.c_float), ("_tail", _ToaJitSpecTail)]
 
 
 class ToaGdOptions(C.Structure):   # include/tinyopt_amd.h toa_gd_options (Options::GD, options.h:147-154)

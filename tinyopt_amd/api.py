@@ -276,6 +276,8 @@ class _LossMixin:
         import copy
         if loss is not None and loss not in LOSS_KINDS:
             raise ValueError(f"unknown loss {loss!r}; one of {sorted(LOSS_KINDS)}")
+        if loss not in (None, "l2") and getattr(getattr(self, "res", None), "large_n", False):
+            _refuse_large_n("no M-estimator (with_loss): the pipeline's loss is per row, an item's is on its squared norm")
         m = copy.copy(self)          # shares the device data
         m.loss, m.th = (loss if loss not in (None, "l2") else None), float(th)
         return m
@@ -295,6 +297,8 @@ class _PriorMixin:
     def with_prior(self, mu: torch.Tensor, W: torch.Tensor):
         import copy
         res = self.res
+        if getattr(res, "large_n", False):
+            _refuse_large_n("no Gaussian prior (with_prior)")
         if res.kind in JitResidual.COST_KINDS:
             _refuse_prior('a scalar cost model (kind="cost" / "cost_grad", GradientDescent) has no residuals to add a prior to')
         if res.manifold != "euclid":
@@ -330,6 +334,11 @@ class _PriorMixin:
         pod = ToaPrior()
         pod.mu_dev, pod.W_dev, pod.rows = self.prior[0].data_ptr(), self.prior[1].data_ptr(), self.prior[2]
         return pod
+
+
+def _refuse_large_n(what: str):
+    raise ValueError(f"a model compiled with large_n=True runs on the launch-per-phase pipeline through Optimize (LM / GN), accumulate, Eval "
+                     f"and CalculateJac only: {what}")
 
 
 def _refuse_prior(what: str):
@@ -559,7 +568,16 @@ class JitResidual:
     ``kind="residual"`` or ``kind="cost"`` body by finite differences instead of Jets: the body is only ever instantiated on the
     plain scalar type (``S`` = ``T``), so it need not be generic (tests/diff.cpp:113-132).  Euclidean parameters; 2 n + 1
     evaluations of the body per item and pass; no ``splits`` and no host controls (stop callbacks, max_duration_ms, the log line).
-    ``CheckGradient(model, x)`` compares the derivatives of ANY model with those differences."""
+    ``CheckGradient(model, x)`` compares the derivatives of ANY model with those differences.
+
+    Beyond 63 parameters — ``large_n=True`` compiles the model for the launch-per-phase pipeline of the wide problems
+    (``DenseRowNatural``'s: a rows kernel over the body, the Gram on the matrix cores, the library's own LDL^T / blocked Cholesky)
+    instead of a wavefront per problem: ``n`` up to 1024 in float32 and 512 in float64 (1 .. 63 is allowed too, so that one text can
+    run through both routes), ``item_scalars`` up to 2048, ``kind="residual"`` (chunked Jets) or ``"accumulate"``, Euclidean
+    parameters, ``diff="ad"``.  ``Optimize`` (LM / GN), ``accumulate``, ``Eval`` and ``CalculateJac`` take such a model; everything
+    else is refused with a sentence: cost kinds and GradientDescent, manifolds, numerical differentiation, ``CheckGradient``,
+    ``with_loss``, ``with_prior``, ``bind_ragged``, ``splits``, the stepping ``Optimizer``, host controls, stream capture of the
+    solve.  Without ``large_n`` a model of 64 parameters is refused as before.  ``stats()`` then describes the rows kernel."""
 
     MANIFOLDS = {"euclid": 0, "se3": 1, "user": 2}
     KINDS = {"residual": 0, "accumulate": 1, "cost": 2, "cost_grad": 3}
@@ -568,7 +586,7 @@ class JitResidual:
 
     def __init__(self, body: str, n: int, item_scalars: int, residuals_per_item: int = 1, header_scalars: int = 0,
                  dtype: torch.dtype = torch.float64, ctx: Optional["Context"] = None, manifold: str = "euclid", kind: str = "residual",
-                 plus_body: Optional[str] = None, x_scalars: int = 0, diff: str = "ad", diff_h: float = 0.0):
+                 plus_body: Optional[str] = None, x_scalars: int = 0, diff: str = "ad", diff_h: float = 0.0, large_n: bool = False):
         """Round 5 — ``manifold="user"``: the caller's own parameter container (the reference's traits::params_trait<T>, traits.h:103-359).
         x is stored as ``x_scalars`` scalars per problem ([P, x_scalars]), ``n`` is the dimension of its tangent and ``plus_body``
         is the body of ``template <class S> void plus(const T* x, const S* d, S* xp)``: xp = x (+) d, written over the scalar type
@@ -583,6 +601,19 @@ class JitResidual:
         if diff not in self.DIFFS:
             raise ValueError(f"unknown diff {diff!r}; one of {sorted(self.DIFFS)}")
         self.diff, self.diff_h = diff, float(diff_h)
+        self.large_n = bool(large_n)
+        if self.large_n:   # (the library refuses the same, toa_model_compile_ex: here before anything is compiled)
+            if kind in self.COST_KINDS:
+                _refuse_large_n('no scalar costs (kind="cost" / "cost_grad") and no GradientDescent')
+            if manifold != "euclid":
+                _refuse_large_n(f"Euclidean parameters only, not manifold={manifold!r}")
+            if diff != "ad":
+                _refuse_large_n(f'diff="ad" only (Jets, or the body\'s own Jacobian rows), not diff={diff!r}')
+            nmax = 1024 if dtype == torch.float32 else 512
+            if not 1 <= self.n <= nmax:
+                _refuse_large_n(f"1 <= n <= 1024 in float32 and <= 512 in float64, not n = {self.n}")
+            if not 0 <= self.kD <= 2048:
+                _refuse_large_n(f"0 <= item_scalars <= 2048, not {self.kD}")
         self.xdim = 12 if manifold == "se3" else (int(x_scalars) if manifold == "user" else self.n)
         self._h = C.c_void_p()
         log = C.create_string_buffer(1 << 16)
@@ -591,6 +622,7 @@ class JitResidual:
         spec.scalars_per_item, spec.header_scalars = self.kD, self.kH
         spec.manifold, spec.kind = self.MANIFOLDS[manifold], self.KINDS[kind]
         spec.diff, spec.diff_h = self.DIFFS[diff], self.diff_h
+        spec.large_n = 1 if self.large_n else 0
         if manifold == "user":
             if not plus_body or int(x_scalars) < 1:
                 raise ValueError('manifold="user" needs plus_body (the body of x (+) d) and x_scalars')
@@ -603,8 +635,8 @@ class JitResidual:
         self.from_cache = bool(fc.value)
 
     def stats(self) -> dict:
-        """What the run-time build of the fused kernel came out as: resident workgroups per compute unit, LDS per workgroup,
-        vector registers per lane, scratch bytes per lane (0 = nothing spilled)."""
+        """What the run-time build of the fused kernel (``large_n=True``: of the rows kernel with J) came out as: resident workgroups
+        per compute unit, LDS per workgroup, vector registers per lane, scratch bytes per lane (0 = nothing spilled)."""
         v = [C.c_int(0) for _ in range(4)]
         check(self.ctx.lib.toa_jit_model_stats(self._h, *[C.byref(t) for t in v]))
         return dict(wg_per_cu=v[0].value, lds_bytes_per_wg=v[1].value, num_regs=v[2].value, scratch_bytes=v[3].value)
@@ -623,6 +655,8 @@ class JitResidual:
         """A RAGGED batch: every problem has its own item count.  data: [total_items, item_scalars] on the GPU, the items of all
         problems one after another; exactly one of ``counts`` ([P] items per problem) / ``offsets`` ([P + 1], see ``ragged_offsets``);
         header: [P, header_scalars].  A count of 0 is legal (that problem ends with kSkipped, x untouched)."""
+        if self.large_n:
+            _refuse_large_n("no ragged batches (bind_ragged)")
         return RaggedJitModel(self, data, counts, offsets, header)
 
     def stats_prior(self, ragged: bool = False) -> dict:
@@ -1057,6 +1091,15 @@ def Optimize(x: torch.Tensor, cost, options: Optional[Options] = None, *, histor
         check(ctx.lib.toa_jit_lm_run_prior(ctx.h, cost.res._h, cost.items, P, cost.packed.data_ptr(), x.data_ptr(), C.byref(pr), C.byref(pod),
                                            C.byref(res), out.counters.data_ptr()))
         return out
+    if isinstance(cost, JitModel) and cost.res.large_n:
+        if splits is not None:
+            _refuse_large_n("no row-split form (splits): the pipeline already spreads a problem's rows over the device")
+        if options.has_host_controls():
+            _refuse_large_n("no stepping form, so no host controls (stop callbacks, max_duration_ms, the log line)")
+        if options.solver_type == Options.GradientDescent:
+            _refuse_large_n("no GradientDescent")
+        if torch.cuda.is_current_stream_capturing():
+            _refuse_large_n("no stream capture of the solve (the host enqueues its passes)")
     if isinstance(cost, JitModel) and cost.res.diff != "ad" and (options.has_host_controls() or splits is not None):
         raise ValueError("a numerically differentiated model (diff=...) runs as one launch per solve: no stop callbacks, max_duration_ms, "
                          "log line or splits (it has no stepping and no row-split form)")
@@ -1188,6 +1231,8 @@ class Optimizer:
             _refuse_prior("no stepping form (Optimizer)")
         if isinstance(cost, JitModel) and cost.res.diff != "ad":
             raise ValueError("a numerically differentiated model (diff=...) has no stepping form")
+        if isinstance(cost, JitModel) and cost.res.large_n:
+            _refuse_large_n("no stepping form (Optimizer)")
         self.x, self.cost = x, cost
         self.ctx = ctx or default_context(x.device.index)
         self.pod = self.options.to_pod()
@@ -1442,6 +1487,8 @@ def CheckGradient(model: "JitModel", x: torch.Tensor, eps: Optional[float] = Non
         _refuse_ragged("no CheckGradient (check the model on a uniform batch: JitResidual.bind)")
     if not isinstance(model, JitModel):
         raise TypeError("CheckGradient takes a bound run-time model (JitResidual.bind)")
+    if model.res.large_n:
+        _refuse_large_n("no CheckGradient (its numeric twin is a one-wavefront model of at most 63 parameters)")
     if method not in ("forward", "central", "fast_central"):
         raise ValueError(f"unknown method {method!r}; one of 'forward', 'central', 'fast_central'")
     _check_call(x, model)

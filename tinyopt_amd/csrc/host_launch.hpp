@@ -104,6 +104,20 @@ struct AccumArgs {
 template <typename F>
 int by_dtype(int dtype, F&& f) { return dtype == TOA_F32 ? f(float()) : f(double()); }
 }  // namespace toa
+// The rows kernel of a run-time model compiled for the launch-per-phase pipeline of large_n.hip (toa_jit_spec::large_n;
+// large_model_rows.hpp): the two instantiations of its code object, their dynamic LDS per workgroup and items per super-step
+// (LargeModelGeom), and the item shape that gives the data stride kH + items x kD.
+namespace toa {
+struct LargeModelRows {
+  hipFunction_t rows_j, rows;   // WANT_J = true / false
+  unsigned lds_j, lds;
+  int items_j, items;
+  int kR, kD, kH;
+};
+}  // namespace toa
+int toa_large_model_lm_run(toa_context* h, int dtype, const toa::LargeModelRows& mr, int n, int num_items, int64_t P, const void* data, void* x,
+                           const toa_options* options, const toa_results* results, uint64_t* counters);
+int toa_large_model_accumulate(toa_context* h, int dtype, const toa::LargeModelRows& mr, const toa::AccumArgs& a);
 int toa_large_accumulate(toa_context* h, int dtype, const toa::AccumArgs& a);
 int toa_large_accumulate_pipeline(toa_context* h, int dtype, const toa::AccumArgs& a);
 

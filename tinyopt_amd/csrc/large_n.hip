@@ -367,6 +367,13 @@ struct LargeArgs {
   int32_t* dok = nullptr;
   const int32_t* dmask = nullptr;
   long long dmask_stride = 0;
+  // a run-time model on this pipeline (toa_jit_spec::large_n; large_model_rows.hpp): its rows kernel writes J —
+  // per problem jstride scalars, rows of ldj scalars (n rounded up to 16 bytes, the pad columns zeros) — and reads mode [P], which
+  // large_model_mode_kernel fills per pass.  (The last members: the offsets of everything above are what the kernels of the natural
+  // family were compiled with.)
+  int ldj = 0;
+  long long jstride = 0;
+  int* mode = nullptr;
   __device__ __forceinline__ bool on(const long long p) const { return active[p] != 0 && !(stepped && stepped[p] != 0); }
   __device__ __forceinline__ bool streams(const long long p) const { return on(p) && !(skip && skip[p] != 0); }   // takes part in the data pass
   __device__ __forceinline__ T* Hcur(const long long p) const {
@@ -854,6 +861,66 @@ __global__ void __launch_bounds__(TRI ? 768 : 1024) large_gram_kernel(const Larg
   else if (tri_pair) run(std::integral_constant<int, 2>{});
   else run(std::integral_constant<int, 1>{});
 }
+// ---- a run-time model on the pipeline: what a problem's rows kernel does this pass (large_model_rows.hpp): 0 = nothing, 1 = residuals
+// only, 2 = residuals and Jacobian — the predicates of large_rows_kernel, as an array of ints the run-time code object can read
+template <typename T>
+__global__ void __launch_bounds__(256) large_model_mode_kernel(const LargeArgs<T> a) {
+  const long long p = blockIdx.x * 256ll + threadIdx.x;
+  if (p >= a.P) return;
+  a.mode[p] = !a.streams(p) ? 0 : ((a.opt.solver_type != 0 || a.st[p].rebuild) ? 2 : 1);
+}
+template <typename T>
+__global__ void __launch_bounds__(256) large_model_ones_kernel(T* __restrict__ v, const size_t count) {
+  const size_t i = blockIdx.x * size_t(256) + threadIdx.x;
+  if (i < count) v[i] = T(1);
+}
+
+// ---- H = J^T J in fp64 for a run-time model's rows (no hand-written fp64 Gram existed: the natural family's goes to the library).
+// One WAVE per (32 x 32 tile of the lower tile triangle, row chunk): four 16 x 16 sub-tiles on v_mfma_f64_16x16x4_f64, four rows per
+// step, the operands straight from J in memory (lane l: row l >> 4 of the step, column l & 15 of the sub-tile; A[i][k] = J[k][i0 + i],
+// B[k][j] = J[k][j0 + j]).  Partials in large_gram_kernel's layout — [p][chunk][tile][32 x 32] — summed over the chunks in fixed order
+// by large_gram_reduce_kernel.  Correct and deterministic first: nothing is staged in LDS, every tile re-reads its columns.
+template <typename T>
+__global__ void __launch_bounds__(64) large_model_gram_kernel(const LargeArgs<T> a, const SyrkGeom geo) {
+  static_assert(sizeof(T) == 8, "fp64 only (fp32: large_gram_kernel over the same J)");
+  typedef double f64x4 __attribute__((ext_vector_type(4)));
+  const long long p = blockIdx.y;
+  if (!a.streams(p)) return;
+  if (!(a.opt.solver_type != 0 || a.st[p].rebuild)) return;
+  const int n = a.n, m = a.m, ld = a.ldj, lane = threadIdx.x;
+  const int t = blockIdx.x % geo.T, chunk = blockIdx.x / geo.T;
+  int ti = 0, tj = t;                           // t -> (ti, tj), ti >= tj, row-major over the lower triangle
+  while (tj > ti) { tj -= ti + 1; ++ti; }
+  const int l15 = lane & 15, l4 = lane >> 4;
+  const T* Jp = a.J + size_t(p) * size_t(a.jstride);
+  const int row0 = chunk * a.gram_rows, row1 = min(m, row0 + a.gram_rows);
+  const int ci0 = 32 * ti + l15, ci1 = ci0 + 16, cj0 = 32 * tj + l15, cj1 = cj0 + 16;
+  f64x4 acc[2][2];
+#pragma unroll
+  for (int i = 0; i < 2; ++i)
+#pragma unroll
+    for (int j = 0; j < 2; ++j) acc[i][j] = f64x4{0, 0, 0, 0};
+  for (int r0 = row0; r0 < row1; r0 += 4) {
+    const int row = r0 + l4;
+    const bool live = row < row1;
+    const T* Jr = Jp + size_t(live ? row : row0) * ld;
+    const T a0 = live && ci0 < n ? Jr[ci0] : T(0), a1 = live && ci1 < n ? Jr[ci1] : T(0);
+    const T b0 = live && cj0 < n ? Jr[cj0] : T(0), b1 = live && cj1 < n ? Jr[cj1] : T(0);
+    acc[0][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b0, acc[0][0], 0, 0, 0);
+    acc[0][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b1, acc[0][1], 0, 0, 0);
+    acc[1][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b0, acc[1][0], 0, 0, 0);
+    acc[1][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b1, acc[1][1], 0, 0, 0);
+  }
+  // C/D map of v_mfma_f64_16x16x4_f64: col = lane & 15, row = (lane >> 4) + 4 reg
+  T* blk = a.gram_part + ((size_t(p) * a.gram_R + chunk) * geo.T + t) * 1024;
+#pragma unroll
+  for (int i = 0; i < 2; ++i)
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+#pragma unroll
+      for (int reg = 0; reg < 4; ++reg) blk[(16 * i + l4 + 4 * reg) * 32 + 16 * j + l15] = acc[i][j][reg];
+}
+
 template <typename T>
 __global__ void __launch_bounds__(256) large_gram_reduce_kernel(const LargeArgs<T> a, const SyrkGeom geo) {
   const long long p = blockIdx.y;
@@ -1985,13 +2052,22 @@ struct LargePlan {
   bool needs_lib, ahead, memo_on, robust;
   int stage_rows, sum_stride;
   size_t sum_bytes;
+  size_t data_stride;              // scalars from one problem's data to the next: m (n + 1), or a model's kH + items x kD
+  const LargeModelRows* model;     // a run-time model's rows kernel instead of the natural family's (NULL: the natural family)
+  int ldj;                         // model: row length of J, n rounded up to 16 bytes
+  int mpad;                        // model: m rounded up to four rows (fp32: what large_gram_kernel sees; the pad rows stay zero)
+  size_t jstride;                  // model: scalars of J per problem, mpad (ldj + 1) — the natural layout [rows][ldj] + one scalar per row
 };
 
 template <typename T>
-LargePlan<T> plan_large(toa_handle h, int n, int m, long long P, const toa_options& opt, LargeMode mode, const T* data) {
+LargePlan<T> plan_large(toa_handle h, int n, int m, long long P, const toa_options& opt, LargeMode mode, const T* data,
+                        const LargeModelRows* model = nullptr) {
   auto al = [](size_t b) { return (b + 255) & ~size_t(255); };
   LargePlan<T> pl;
   pl.mode = mode; pl.n = n; pl.m = m; pl.P = P; pl.nn = size_t(n) * n;
+  pl.model = model;
+  pl.data_stride = model ? size_t(model->kH) + size_t(m / model->kR) * size_t(model->kD) : size_t(m) * (size_t(n) + 1);
+  pl.ldj = 0; pl.mpad = 0; pl.jstride = 0;
   pl.max_tries = opt.max_consec_failures > 0 ? (opt.max_consec_failures > 1 ? opt.max_consec_failures : 1) : 255;
   pl.max_passes = (long long)(opt.max_iters + 2 + (opt.check_final_cost ? 1 : 0)) * (long long)(pl.max_tries + 1);
   pl.seam = mode == LargeMode::Accumulate;   // toa_accumulate: one data pass, no Build (seam_out says where the results go)
@@ -2002,7 +2078,7 @@ LargePlan<T> plan_large(toa_handle h, int n, int m, long long P, const toa_optio
   constexpr int VEC = 16 / int(sizeof(T));
   // (n > 1024, round 5: the general rows kernel + the library's GEMM / GEMV / factorisation — the vectorised rows kernel keeps at most
   //  eight 16-byte vectors of a row per lane, the hand-written Gram's LDS stage ends at 1024 columns)
-  const bool vec_shape = n <= 1024 && n % VEC == 0 && (size_t(m) * (n + 1)) % VEC == 0 && reinterpret_cast<uintptr_t>(data) % 16 == 0;
+  const bool vec_shape = !model && n <= 1024 && n % VEC == 0 && (size_t(m) * (n + 1)) % VEC == 0 && reinterpret_cast<uintptr_t>(data) % 16 == 0;
   const int nv = n / VEC;
   int LPR = 1;
   while (LPR * 2 <= std::min(64, nv)) LPR *= 2;
@@ -2019,13 +2095,21 @@ LargePlan<T> plan_large(toa_handle h, int n, int m, long long P, const toa_optio
   const long long wg_target = std::min<long long>((long long)h->num_cus * 16 / std::max<long long>(1, P) + 1, h->num_cus);
   pl.row_blocks = unsigned(std::max<long long>(1, std::min<long long>((m + 4 * (pl.vec_ok ? pl.RPW : 4) - 1) / (4 * (pl.vec_ok ? pl.RPW : 4)), wg_target)));
   pl.gslots = pl.vec_ok ? int(pl.row_blocks) * 4 : 0;
+  if (model) {   // a wave per super-step of model->items_j items; every wave leaves its partial J^T r (large_model_rows.hpp)
+    const long long nss = ((long long)(m / model->kR) + model->items_j - 1) / model->items_j;
+    pl.row_blocks = unsigned(std::max<long long>(1, std::min<long long>((nss + 3) / 4, wg_target)));
+    pl.gslots = int(pl.row_blocks) * 4;
+    pl.ldj = (n + VEC - 1) / VEC * VEC;
+    pl.mpad = (m + 3) & ~3;
+    pl.jstride = size_t(pl.mpad) * (size_t(pl.ldj) + 1);
+  }
   // H = J^T J: the hand-written LDS-staged Gram (large_gram_kernel) for fp32 rows that are 16-byte aligned; the library GEMM
   // otherwise (fp64, odd shapes) or with toa_tuning::large_library_gram.  Same box, 128 problems x n = 256 x m = 8192 fp32
   // (profiles/r03_ab_log.md): rocblas_sgemm_batched 1.22 ms per pass with every problem rebuilding (the full square,
   // 113 TFLOP/s) plus the J = diag(s) A round trip through HBM in the rows kernel (0.43 -> 0.23 ms without it); this kernel
   // 0.74 ms (the lower tile triangle only: 56 % of the flops, at 104 TFLOP/s issued).
   const bool force_gemm = h->tune.large_library_gram != 0;
-  pl.own_gram = sizeof(T) == 4 && pl.vec_ok && !force_gemm && n % 4 == 0;
+  pl.own_gram = model ? true : sizeof(T) == 4 && pl.vec_ok && !force_gemm && n % 4 == 0;   // (a model: large_model_lm_run_t refuses the library's Gram)
   pl.gram_R = 1; pl.gram_rows = (m + 3) & ~3;
   pl.geo = syrk_geom(n);
   const SyrkGeom& geo = pl.geo;
@@ -2036,6 +2120,12 @@ LargePlan<T> plan_large(toa_handle h, int n, int m, long long P, const toa_optio
     const long long want_wgs = (long long)h->num_cus * 4, per_chunk = P * geo.groups;
     pl.gram_R = int(std::max<long long>(1, std::min<long long>(256, (want_wgs + per_chunk - 1) / per_chunk)));   // (a FEW huge problems: up to 256 row chunks each)
     pl.gram_rows = (((m + pl.gram_R - 1) / pl.gram_R) + geo.K - 1) / geo.K * geo.K;
+    pl.gram_R = (m + pl.gram_rows - 1) / pl.gram_rows;
+  }
+  if (model && sizeof(T) == 8) {   // large_model_gram_kernel: a wave per (tile, row chunk); about sixteen waves per compute unit, four rows per step
+    const long long want_waves = (long long)h->num_cus * 16, per_chunk = P * geo.T;
+    pl.gram_R = int(std::max<long long>(1, std::min<long long>(256, (want_waves + per_chunk - 1) / per_chunk)));
+    pl.gram_rows = (((m + pl.gram_R - 1) / pl.gram_R) + 3) / 4 * 4;
     pl.gram_R = (m + pl.gram_rows - 1) / pl.gram_rows;
   }
   // use_ldlt = false (gn.h:157-162): dx = -H.inverse() * g "without any checks on invertibility" (options.h:59) — a general LU
@@ -2088,14 +2178,15 @@ void large_scratch_arrays(LargeArgs<T>& a, int*& ipiv, const LargePlan<T>& pl, V
   v(a.stepped, 1);   // (the slot is there in every form, the pointer only in the stepping form: large_lm_run_t clears it otherwise)
   v(a.gnew, n); v(a.rhs, n);
   v(a.Hnew, nn); v(a.work, nn);
-  v(a.J, pl.own_gram ? 0 : m * n);   // J = diag(s) A is only materialised for the library GEMM
+  v(a.J, pl.model ? pl.jstride : pl.own_gram ? 0 : m * n);   // J = diag(s) A is only materialised for the library GEMM; a model's rows kernel writes its J
   v(a.r, m);
-  v(a.sc, pl.own_gram ? m : 0);
+  v(a.sc, !pl.own_gram ? 0 : !pl.model ? m : sizeof(T) == 4 ? size_t(pl.mpad) : 0);   // (a model in fp32: ones, see enqueue_pass)
   v(a.gram_part, pl.own_gram ? size_t(pl.gram_R) * pl.geo.T * 1024 : 0);
   v.fixed(a.summary, pl.sum_bytes);   // not per problem: two (four: stepping) counts per pass, a run of them per lane
   v(a.gpart, size_t(std::max(pl.gslots, 1)) * n);   // (no lanes without the vectorised rows kernel: the one slot of gslots = 0 is never shifted)
   v(a.jptr, 1); v(a.hptr, 1);
   v(ipiv, pl.lu ? n : 0);
+  if (pl.model) v(a.mode, 1);
   if (pl.robust) { v(a.lossv, m); v(a.ninl, 1); }
   if (pl.memo_on) {
     v(a.lin_ninl, 1); v(a.memo_ninl, 1);
@@ -2137,7 +2228,7 @@ void shift_large(LargeArgs<T>& a, const LargePlan<T>& pl, long long p0, long lon
   large_state_arrays(a, pl, s);
   large_scratch_arrays(a, no_pivots, pl, s);
   a.P = Pl;
-  a.data += size_t(p0) * pl.m * (size_t(pl.n) + 1);
+  a.data += size_t(p0) * pl.data_stride;
   a.x += p0 * pl.n;
   a.res = results_at(a.res, p0, pl.n);
 }
@@ -2162,9 +2253,37 @@ struct LargeRun {
     if (wait_first) HIP_TRY(hipStreamWaitEvent(ls, wait_first, 0));
     const dim3 rgrid(pl.row_blocks, unsigned(Pl));
     const size_t xs_bytes = size_t(n) * sizeof(T);
-    if (!pl.vec_ok) hipLaunchKernelGGL(large_rows_kernel<T>, rgrid, dim3(256), xs_bytes, ls, la);
-    else launch_rows_vec<T>(pl.KV, rgrid, xs_bytes, ls, la, pl.LPR);
-    if (pl.own_gram) {
+    if (pl.model) {   // the model's own code object (large_model_rows.hpp), told per problem what this pass wants of it
+      hipLaunchKernelGGL(large_model_mode_kernel<T>, dim3(unsigned((Pl + 255) / 256)), dim3(256), 0, ls, la);
+      HIP_TRY(hipGetLastError());
+      const T* d_ = la.data; const T* x_ = la.x; T* r_ = la.r; T* J_ = la.J; T* gp_ = la.gpart;
+      const int* md_ = la.mode;
+      int items_ = m / pl.model->kR, ldj_ = pl.ldj, all_ = 0, gs_ = pl.gslots;
+      long long ds_ = (long long)pl.data_stride, js_ = (long long)pl.jstride;
+      void* args[] = {&d_, &x_, &items_, &ds_, &r_, &J_, &ldj_, &js_, &md_, &all_, &gp_, &gs_};
+      const hipError_t e = hipModuleLaunchKernel(pl.model->rows_j, rgrid.x, rgrid.y, 1, 256, 1, 1, pl.model->lds_j, ls, args, nullptr);
+      if (e != hipSuccess) return toa_fail(TOA_E_HIP, std::string("large-n run-time model: rows kernel launch: ") + hipGetErrorString(e));
+    } else if (!pl.vec_ok) {
+      hipLaunchKernelGGL(large_rows_kernel<T>, rgrid, dim3(256), xs_bytes, ls, la);
+    } else {
+      launch_rows_vec<T>(pl.KV, rgrid, xs_bytes, ls, la, pl.LPR);
+    }
+    if (pl.model) {   // H = J^T J over the J just written
+      const SyrkGeom& geo = pl.geo;
+      if constexpr (sizeof(T) == 4) {
+        // large_gram_kernel as it is, shown J as a problem of the natural layout: mpad rows of ldj columns (then one unused scalar per
+        // row, where the natural family keeps b), the row scales all ones — x 1 is exact; the pad rows and columns are zeros
+        LargeArgs<T> ga = la;
+        ga.data = la.J; ga.n = pl.ldj; ga.m = pl.mpad;
+        const dim3 ggrid(unsigned(geo.groups * pl.gram_R), unsigned(Pl)), gblock(unsigned(geo.waves * 64));
+        const size_t glds = size_t(2) * geo.K * geo.ns * sizeof(T) + 256;
+        launch_gram<T>(geo, pl.gram_tri, ggrid, gblock, glds, ls, ga);
+      } else {
+        hipLaunchKernelGGL(large_model_gram_kernel<T>, dim3(unsigned(geo.T * pl.gram_R), unsigned(Pl)), dim3(64), 0, ls, la, geo);
+      }
+      hipLaunchKernelGGL(large_gram_reduce_kernel<T>, dim3(unsigned(geo.T), unsigned(Pl)), dim3(256), 0, ls, la, geo);
+      if (record_after_gram) HIP_TRY(hipEventRecord(record_after_gram, ls));
+    } else if (pl.own_gram) {
       if constexpr (sizeof(T) == 4) {
         const SyrkGeom& geo = pl.geo;
         const dim3 ggrid(unsigned(geo.groups * pl.gram_R), unsigned(Pl)), gblock(unsigned(geo.waves * 64));
@@ -2362,8 +2481,9 @@ struct LargeRun {
 template <typename T>
 int large_lm_run_t(toa_handle h, int n, int m, int64_t P, const T* data, T* x, const toa_options& opt,
                    const toa_results& res, uint64_t* counters, LargeMode mode = LargeMode::Solve, void* state = nullptr,
-                   int32_t* active_dev = nullptr, const int32_t* stop_request = nullptr, const LargeSeamOut<T>* seam_out = nullptr) {
-  const LargePlan<T> pl = plan_large<T>(h, n, m, P, opt, mode, data);
+                   int32_t* active_dev = nullptr, const int32_t* stop_request = nullptr, const LargeSeamOut<T>* seam_out = nullptr,
+                   const LargeModelRows* model = nullptr) {
+  const LargePlan<T> pl = plan_large<T>(h, n, m, P, opt, mode, data, model);
   auto al = [](size_t b) { return (b + 255) & ~size_t(255); };
   const size_t b_i = al(size_t(P) * sizeof(int)), b_vec = al(size_t(P) * n * sizeof(T));
   LargeArgs<T> a{};
@@ -2377,6 +2497,8 @@ int large_lm_run_t(toa_handle h, int n, int m, int64_t P, const T* data, T* x, c
   a.active_out = active_dev; a.stop_request = stop_request;
   a.own_gram = pl.own_gram ? 1 : 0; a.gram_R = pl.gram_R; a.gram_rows = pl.gram_rows;
   a.gslots = pl.gslots;
+  a.ldj = pl.ldj; a.jstride = (long long)pl.jstride;
+  if (!pl.model) a.mode = nullptr;
   a.hslots = pl.memo_on ? 2 : 1;
   a.loss = h->loss; a.th2 = T(h->loss_th2);
   hipStream_t st = h->stream;
@@ -2405,6 +2527,12 @@ int large_lm_run_t(toa_handle h, int n, int m, int64_t P, const T* data, T* x, c
     HIP_TRY(hipGetLastError());
     if (mode == LargeMode::Begin) return TOA_OK;
     if (pl.seam) hipLaunchKernelGGL(large_seam_prep_kernel<T>, dim3(unsigned((P + 255) / 256)), dim3(256), 0, st, a, seam_out->want_grad);
+  }
+  if (pl.model && sizeof(T) == 4) {   // what large_gram_kernel reads beside the rows kernel's J: zero pad rows, unit row scales
+    HIP_TRY(hipMemsetAsync(a.J, 0, size_t(P) * pl.jstride * sizeof(T), st));
+    const size_t cnt = size_t(P) * size_t(pl.mpad);
+    hipLaunchKernelGGL(large_model_ones_kernel<T>, dim3(unsigned((cnt + 255) / 256)), dim3(256), 0, st, a.sc, cnt);
+    HIP_TRY(hipGetLastError());
   }
   HIP_TRY(hipMemsetAsync(a.summary, 0, pl.sum_bytes, st));
   if (pl.stepping) HIP_TRY(hipMemsetAsync(a.stepped, 0, b_i, st));
@@ -2552,6 +2680,45 @@ int toa_large_lm_run(toa_handle h, int dtype, int n, int m, int64_t P, const voi
       using T = decltype(tag);
       return toa::large_lm_run_t<T>(h, n, m, Ps, static_cast<const T*>(data) + size_t(p0) * size_t(m) * (size_t(n) + 1),
                                     static_cast<T*>(x) + size_t(p0) * size_t(n), *options, r, counters);
+    });
+  });
+}
+
+// A run-time model on the pipeline (toa_jit_spec::large_n; jit.hip): the whole solve, every stage a kernel of this library under
+// default options — the model's rows kernel, the Gram over its J, our factorisation.  Slices of 65 535 problems step by the
+// model's data stride.
+int toa_large_model_lm_run(toa_handle h, int dtype, const toa::LargeModelRows& mr, int n, int num_items, int64_t P, const void* data, void* x,
+                           const toa_options* options, const toa_results* results, uint64_t* counters) {
+  if (h->tune.large_library_gram)
+    return toa_fail(TOA_E_UNSUPPORTED, "large-n run-time model: toa_tuning::large_library_gram is not available for a run-time model (the Gram runs over the "
+                                       "padded J of its rows kernel: large_gram_kernel in fp32, large_model_gram_kernel in fp64)");
+  const size_t stride = size_t(mr.kH) + size_t(num_items) * size_t(mr.kD);
+  return toa::by_slices(P, true, [&](int64_t p0, int64_t Ps) -> int {
+    const toa_results r = results_at(*results, p0, n);
+    return toa::by_dtype(dtype, [&](auto tag) -> int {
+      using T = decltype(tag);
+      return toa::large_lm_run_t<T>(h, n, num_items * mr.kR, Ps, static_cast<const T*>(data) + size_t(p0) * stride,
+                                    static_cast<T*>(x) + size_t(p0) * size_t(n), *options, r, counters, toa::LargeMode::Solve, nullptr, nullptr, nullptr,
+                                    nullptr, &mr);
+    });
+  });
+}
+// ... and its Accumulate seam: one data pass (a.m = items x kR rows)
+int toa_large_model_accumulate(toa_handle h, int dtype, const toa::LargeModelRows& mr, const toa::AccumArgs& a) {
+  if (h->tune.large_library_gram)
+    return toa_fail(TOA_E_UNSUPPORTED, "large-n run-time model: toa_tuning::large_library_gram is not available for a run-time model");
+  toa_options opt;
+  toa_options_default(&opt);
+  toa_results res{};
+  const size_t n = size_t(a.n), stride = size_t(mr.kH) + size_t(a.m / mr.kR) * size_t(mr.kD);
+  return toa::by_slices(a.P, false, [&](int64_t p0, int64_t Ps) -> int {
+    return toa::by_dtype(dtype, [&](auto tag) -> int {
+      using T = decltype(tag);
+      const toa::LargeSeamOut<T> o{a.g ? static_cast<T*>(a.g) + size_t(p0) * n : nullptr, a.H ? static_cast<T*>(a.H) + size_t(p0) * n * n : nullptr,
+                                   a.cost + p0, a.nres ? a.nres + p0 : nullptr, a.want_grad};
+      return toa::large_lm_run_t<T>(h, a.n, a.m, Ps, static_cast<const T*>(a.data) + size_t(p0) * stride,
+                                    const_cast<T*>(static_cast<const T*>(a.x)) + size_t(p0) * n, opt, res, nullptr, toa::LargeMode::Accumulate,
+                                    nullptr, nullptr, nullptr, &o, &mr);
     });
   });
 }

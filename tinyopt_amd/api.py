@@ -1017,6 +1017,28 @@ def _results_pod(out: Output) -> ToaResults:
     return res
 
 
+def _run_prologue(x: torch.Tensor, cost, n: int, options: Options, history: bool, ctx: Context, out: Optional[Output], zero_counters: bool,
+                  *, no_hessian: bool = False, gd: bool = False):
+    """What every one-launch run does before its library call: the options as a pod, the caller's ``out`` (its counters zeroed
+    unless ``zero_counters`` is off) or a fresh one for n unknowns, the results pod over it, the cost's loss on the handle.
+    Returns (pod, out, res).  ``no_hessian``: a path that forms no final Hessian allocates none, whatever options.hessian.save_last
+    says; ``gd``: ... and hands the library none either (gradient descent, optimizer.h:313)."""
+    pod = options.to_pod()
+    if out is None:
+        if no_hessian:
+            import copy
+            options = copy.deepcopy(options)
+            options.hessian.save_last = False
+        out = _alloc_output(x.shape[0], n, options, history, x.device)
+    elif zero_counters:
+        out.counters.zero_()
+    res = _results_pod(out)
+    if gd:
+        res.final_hessian = None
+    _apply_loss(ctx, cost)
+    return pod, out, res
+
+
 def Optimize(x: torch.Tensor, cost, options: Optional[Options] = None, *, history: bool = False,
              ctx: Optional[Context] = None, out: Optional[Output] = None, splits: Optional[int] = None,
              zero_counters: bool = True, keep_order: bool = False) -> Output:
@@ -1041,34 +1063,16 @@ def Optimize(x: torch.Tensor, cost, options: Optional[Options] = None, *, histor
     if isinstance(cost, BundleAdjustment):
         if options.has_host_controls() or splits is not None:
             raise ValueError("BundleAdjustment runs as one launch per solve: no stop callbacks / splits")
-        pod = options.to_pod()
+        pod, out, res = _run_prologue(x, cost, 1, options, history, ctx, out, zero_counters, no_hessian=True)
         pod.save_last = 0
-        if out is None:
-            import copy
-            o2 = copy.deepcopy(options)
-            o2.hessian.save_last = False
-            out = _alloc_output(P, 1, o2, history, x.device)
-        elif zero_counters:
-            out.counters.zero_()
-        res = _results_pod(out)
-        _apply_loss(ctx, cost)
         check(ctx.lib.toa_ba_run(ctx.h, _dtype_code(x.dtype), cost.ncam, cost.npts, P, cost.packed.data_ptr(), x.data_ptr(),
                                  C.byref(pod), C.byref(res), out.counters.data_ptr()))
         return out
     if isinstance(cost, BundleAdjustmentLists):
         if options.stop_callback is not None or options.stop_callback2 is not None or splits is not None:
             raise ValueError("BundleAdjustmentLists: no stop callbacks / splits (max_duration_ms is honoured)")
-        pod = options.to_pod()
+        pod, out, res = _run_prologue(x, cost, 1, options, history, ctx, out, zero_counters, no_hessian=True)
         pod.save_last = 0
-        if out is None:
-            import copy
-            o2 = copy.deepcopy(options)
-            o2.hessian.save_last = False
-            out = _alloc_output(P, 1, o2, history, x.device)
-        elif zero_counters:
-            out.counters.zero_()
-        res = _results_pod(out)
-        _apply_loss(ctx, cost)
         check(ctx.lib.toa_ba_lists_run(ctx.h, _dtype_code(x.dtype), cost.ncam, cost.npts, cost.nobs, P, cost.intr.data_ptr(),
                                        cost.obs_cam.data_ptr(), cost.obs_pt.data_ptr(), cost.obs_uv.data_ptr(), x.data_ptr(),
                                        C.byref(pod), C.byref(res), out.counters.data_ptr(), float(options.max_duration_ms or 0.0)))
@@ -1080,13 +1084,7 @@ def Optimize(x: torch.Tensor, cost, options: Optional[Options] = None, *, histor
             _refuse_prior("no stepping form, so no host controls (stop callbacks, max_duration_ms, the log line)")
         if options.solver_type == Options.GradientDescent:
             _refuse_prior("no GradientDescent")
-        pod = options.to_pod()
-        if out is None:
-            out = _alloc_output(P, n, options, history, x.device)
-        elif zero_counters:
-            out.counters.zero_()
-        res = _results_pod(out)
-        _apply_loss(ctx, cost)
+        pod, out, res = _run_prologue(x, cost, n, options, history, ctx, out, zero_counters)
         pr = cost._prior_pod()
         check(ctx.lib.toa_jit_lm_run_prior(ctx.h, cost.res._h, cost.items, P, cost.packed.data_ptr(), x.data_ptr(), C.byref(pr), C.byref(pod),
                                            C.byref(res), out.counters.data_ptr()))
@@ -1110,13 +1108,7 @@ def Optimize(x: torch.Tensor, cost, options: Optional[Options] = None, *, histor
             if splits is not None or out is not None:
                 raise ValueError("stop callbacks / max_duration_ms run through the stepping form: splits / out are not taken")
             return _optimize_with_host_controls(x, cost, options, history, ctx)
-        pod = options.to_pod()
-        if out is None:
-            out = _alloc_output(P, n, options, history, x.device)
-        elif zero_counters:
-            out.counters.zero_()
-        res = _results_pod(out)
-        _apply_loss(ctx, cost)
+        pod, out, res = _run_prologue(x, cost, n, options, history, ctx, out, zero_counters)
         if splits is None:   # the library decides (row-split for few, huge problems: P * 4 <= #CUs and m >= 512)
             check(ctx.lib.toa_jit_lm_run(ctx.h, cost.res._h, cost.items, P, cost.packed.data_ptr(), x.data_ptr(), C.byref(pod),
                                          C.byref(res), out.counters.data_ptr()))
@@ -1128,13 +1120,7 @@ def Optimize(x: torch.Tensor, cost, options: Optional[Options] = None, *, histor
         if splits is not None or out is not None:
             raise ValueError("stop callbacks / max_duration_ms run through the stepping form: splits / out are not taken")
         return _optimize_with_host_controls(x, cost, options, history, ctx)
-    pod = options.to_pod()
-    if out is None:
-        out = _alloc_output(P, n, options, history, x.device)
-    elif zero_counters:
-        out.counters.zero_()
-    res = _results_pod(out)
-    _apply_loss(ctx, cost)
+    pod, out, res = _run_prologue(x, cost, n, options, history, ctx, out, zero_counters)
     if splits is None:   # the library decides (row-split for few, huge problems)
         check(ctx.lib.toa_lm_run(ctx.h, cost.model_id, _dtype_code(x.dtype), n, cost.m, P, cost.packed.data_ptr(),
                                  x.data_ptr(), C.byref(pod), C.byref(res), out.counters.data_ptr()))
@@ -1154,20 +1140,11 @@ def _optimize_gd(x: torch.Tensor, cost: "JitModel", options: Options, history: b
         raise ValueError("GradientDescent: no row-split form (splits)")
     from ._capi import ToaGdOptions
     P = x.shape[0]
-    pod = options.to_pod()
     gd = ToaGdOptions()
     ctx.lib.toa_gd_options_default(C.byref(gd))
     gd.lr = float(options.gd.lr)
-    if out is None:
-        import copy
-        o2 = copy.deepcopy(options)
-        o2.hessian.save_last = False
-        out = _alloc_output(P, cost.n, o2, history, x.device)
-    elif zero_counters:
-        out.counters.zero_()
-    res = _results_pod(out)
-    res.final_hessian = None
-    _apply_loss(ctx, cost)   # (a loss on a scalar cost is refused by the library)
+    # (a loss on a scalar cost is refused by the library)
+    pod, out, res = _run_prologue(x, cost, cost.n, options, history, ctx, out, zero_counters, no_hessian=True, gd=True)
     check(ctx.lib.toa_jit_gd_run(ctx.h, cost.res._h, cost.items, P, cost.packed.data_ptr(), x.data_ptr(), C.byref(pod), C.byref(gd),
                                  C.byref(res), out.counters.data_ptr()))
     return out
@@ -1184,25 +1161,13 @@ def _optimize_ragged(x: torch.Tensor, cost: "RaggedJitModel", options: Options, 
         _refuse_prior("no GradientDescent")
     P = x.shape[0]
     gd_run = cost.res.kind in JitResidual.COST_KINDS and options.solver_type == Options.GradientDescent
-    pod = options.to_pod()
-    if out is None:
-        o2 = options
-        if gd_run:
-            import copy
-            o2 = copy.deepcopy(options)
-            o2.hessian.save_last = False
-        out = _alloc_output(P, cost.n, o2, history, x.device)
-    elif zero_counters:
-        out.counters.zero_()
-    res = _results_pod(out)
-    _apply_loss(ctx, cost)
+    pod, out, res = _run_prologue(x, cost, cost.n, options, history, ctx, out, zero_counters, no_hessian=gd_run, gd=gd_run)
     flags = 1 if keep_order else 0
     if gd_run:
         from ._capi import ToaGdOptions
         gd = ToaGdOptions()
         ctx.lib.toa_gd_options_default(C.byref(gd))
         gd.lr = float(options.gd.lr)
-        res.final_hessian = None
         check(ctx.lib.toa_jit_gd_run_ragged(ctx.h, cost.res._h, *cost._ragged_args(), P, cost.data.data_ptr(), x.data_ptr(), C.byref(pod),
                                             C.byref(gd), C.byref(res), out.counters.data_ptr(), flags))
     elif cost.prior is not None:

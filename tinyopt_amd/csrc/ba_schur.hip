@@ -619,6 +619,8 @@ __global__ void __launch_bounds__(256, TOA_BA_WGS) ba_schur_kernel(const BaParam
       // cores (ldlt_wg.hpp; the one-wavefront register factorisation used here before took 33 us of a 145 us iteration at
       // C = 8 in fp64).  It factors in place, so the image is parked in `part` (free since the fold) first: a pivot that is
       // not safely positive falls back to the pivoted factorisation with the reference's acceptance rule on the restored image.
+      // (That fallback is also what steps over a camera whose mask row is empty — a zero block row of M — with dc = 0, as the dense
+      //  oracle does; the lists form, whose solvers do not pivot, gives such a camera the identity block: bl_build_kernel.)
       for (int e = tid; e < n * n; e += 256) part[e] = L.M[(e / n) * L.LD + (e % n)];
       __syncthreads();
       constexpr int NBS = NBM + (THIN > 1 ? 1 : 0);   // 16-column panels covering n = 16 NBM + max(THIN - 1, 0) (- 1 without a thin tail)
@@ -1215,9 +1217,20 @@ __global__ void __launch_bounds__(256) bl_build_kernel(const BlParams* __restric
     }
   }
   __syncthreads();
-  if (built && is_lm && S.lambda > T(0)) {  // lm.h:108-117, s in double; the points' diagonal is scaled in bl_psolve
-    const double s = S.rebuild ? 1.0 + double(S.lambda) : (1.0 + double(S.lambda)) / (1.0 + double(S.prev_lambda));
-    for (int i = tid; i < n; i += 256) w[wk.Ud + i] = T(double(w[wk.Ud + i]) * s);
+  if (built) {  // lm.h:108-117, s in double; the points' diagonal is scaled in bl_psolve
+    const bool damp = is_lm && S.lambda > T(0);
+    const double s = !damp ? 1.0 : S.rebuild ? 1.0 + double(S.lambda) : (1.0 + double(S.lambda)) / (1.0 + double(S.prev_lambda));
+    // A camera that sees nothing has U_c = 0 and no W: a zero block row of S, which no factorisation without pivoting gets past.  Its
+    // diagonal — all the Schur kernels add to that block of S — becomes one: the identity block; its right-hand side is zero, so
+    // dc = 0, the step of the dense pivoted LDL^T (pseudo-inverse).  (Here and not in the Schur epilogues: the test rides on the
+    // load of the diagonal this loop makes anyway; there it was 0.3 % of a pass of the 64-camera benchmark.)
+    const int* cs = prm->iwork + size_t(p) * ix.total + ix.cam_start;
+    for (int i = tid; i < n; i += 256) {
+      const bool blind = cs[i / 6] == cs[i / 6 + 1];
+      const T u = w[wk.Ud + i];
+      if (blind) w[wk.Ud + i] = T(1);
+      else if (damp) w[wk.Ud + i] = T(double(u) * s);
+    }
   }
   if (tid == 0) { fl[3] = built ? 1 : 0; fl[4] = 0; fl[5] = 0; }
 }

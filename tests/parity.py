@@ -40,7 +40,7 @@ def first_divergence(errs_a, succ_a, ka, errs_b, succ_b, kb, rtol=1e-7, atol=1e-
     return None if ka == kb else min(ka, kb)
 
 
-def _last_accepted(errs, succ, k):
+def last_accepted(errs, succ, k):
     """Cost of the last accepted iteration before k (iteration 0 is always accepted, optimizer.h:441)."""
     acc = [i for i in range(k) if succ[i] or i == 0]
     return errs[acc[-1]] if acc else None
@@ -54,7 +54,7 @@ def _threshold_straddle(pod, stop_short, errs, d2, succ, j, rtol):
     if stop_short == 1 and pod.min_error > 0:                       # kMinError: err < min_error
         return abs(err - pod.min_error) <= rtol * pod.min_error
     if stop_short == 2 and pod.min_rerr_dec > 0 and j >= 1:         # kMinRelError: 0 < rel_derr < min_rerr_dec
-        last_ok = _last_accepted(errs, succ, j)
+        last_ok = last_accepted(errs, succ, j)
         rel = (last_ok - err) / last_ok if last_ok else 0.0
         # rel is a difference of two costs: its own round-off is err_noise / last_ok
         return abs(rel - pod.min_rerr_dec) <= rtol or abs(rel) <= rtol
@@ -99,7 +99,7 @@ def check_trajectories(gpu, ref, dtype, pod, *, tol=None, x_scale=1.0, label="")
             assert np.isclose(ge[j], re_[j], rtol=t["err_rtol"], atol=1e-300), (label, p, j, "different point", ge[j], re_[j])
         else:
             j = k - 1                                 # same flags, but only one side's stop test fired after iteration k-1
-        last_ok = _last_accepted(ge, gs, j) if j >= 1 else ge[0]
+        last_ok = last_accepted(ge, gs, j) if j >= 1 else ge[0]
         gap = abs(ge[j] - last_ok)
         at_floor = gap <= t["floor_rtol"] * max(abs(last_ok), 1e-300)
         if not at_floor and k >= min(gk, rk):         # a stop threshold straddled by round-off (the shorter run stopped)

@@ -4,7 +4,8 @@ a 32-observation chunk, the second and third camera tile, the library Cholesky p
 `large_library_solver`), the general LU at 6 C = 144, fp32 beyond 32 cameras, scenes of one batch that stop at different passes,
 points no camera sees and a camera that sees nothing.  Everything is compared with the oracle (`oracle.ba_lm`: the reference's dense
 (6 C + 3 N)^2 Hessian with pivoted LDL^T) — whole trajectories as tests/test_gpu_ba_lists.py does, and the first two steps against a
-yardstick taken from the oracle alone (`test_first_steps_tightly`).  Every oracle result is computed once per (scene, number
+yardstick taken from the oracle alone (`test_first_steps_tightly`).  Section 7 pins the step bookkeeping both forms share
+(lm_device.hpp) against the oracle, option branch by option branch.  Every oracle result is computed once per (scene, number
 format, options) and shared (`_REF`)."""
 import contextlib
 
@@ -12,7 +13,7 @@ import numpy as np
 import pytest
 import torch
 
-from parity import check_trajectories, gpu_dict
+from parity import check_trajectories, first_divergence, gpu_dict, last_accepted
 
 pytestmark = pytest.mark.gpu
 
@@ -324,3 +325,182 @@ def test_first_steps_tightly(ta, oracle, name, form, dtype, knob):
     step = float(np.abs(r64["x"] - x0).max())
     print(f"FIRST {name} {form} {np.dtype(dtype).name}: step {step:.3e} gap32 {gap32:.3e} err {err:.3e} ratio {err / bound:.3f}")
     assert err <= bound, (name, form, err, bound, gap32)
+
+
+# ---- 7. every branch of the step bookkeeping, in both forms -------------------------------------------------------------------------
+def _variant(ta, key):
+    o = ta.Options()
+    if key == "final_cost": o.check_final_cost = True; o.max_iters = 3                        # the final cost-only pass
+    elif key == "one_iter": o.max_iters = 1                                                   # the iteration bound
+    elif key == "damping10": o.lm.damping_init = 10.0                                         # a chain of GoodSteps
+    elif key == "step_quality": o.use_step_quality_approx = True                              # the step-quality branch of GoodStep
+    elif key == "clip5": o.grad_clipping = 0.5; o.max_iters = 5                               # rejected steps, roll-backs, eval-only iterations
+    elif key == "clip_total2": o.grad_clipping = 0.5; o.max_iters = 8; o.max_total_failures = 2       # kMaxNoDecr
+    elif key == "clip_consec2": o.grad_clipping = 0.5; o.max_iters = 8; o.max_consec_failures = 2     # kMaxConsecNoDecr
+    elif key == "clip_total1": o.grad_clipping = 0.5; o.max_iters = 8; o.max_total_failures = 1       # the FIRST rejection: roll back, kMaxNoDecr
+    elif key == "clip_consec1": o.grad_clipping = 0.5; o.max_iters = 8; o.max_consec_failures = 1     # ... roll back, kMaxConsecNoDecr
+    elif key == "clip_final_cost": o.grad_clipping = 0.5; o.max_iters = 4; o.check_final_cost = True  # rejections under the final-cost pass
+    elif key == "min_h_diag": o.hessian.check_min_H_diag = 1e9                                # Build fails, re-damps, retries to the consecutive limit
+    elif key == "min_error": o.min_error = 1e9                                                # immediate kMinError
+    else: raise KeyError(key)
+    return o
+
+
+# (Gauss-Newton is absent on purpose: a BA Hessian has seven free gauge directions, so without damping the verdict of the
+#  factorisation is decided by rounding — not a property of the code under test.)
+_VARIANTS = ["final_cost", "one_iter", "damping10", "step_quality", "clip5", "clip_total2", "clip_consec2", "clip_final_cost",
+             "min_h_diag", "min_error", "clip_total1", "clip_consec1"]
+# The four variants with grad_clipping reject steps, and a rejected step cannot be followed against the oracle to the end: the
+# iteration after a roll-back evaluates the restored point, so `err < final_cost` (optimizer.h:428-429) compares two costs that
+# are equal in exact arithmetic and is decided by the last bit of (x (+) dx) (+) -dx — SE3 poses never come back bit for bit.
+# Measured on the MI355X before the bookkeeping moved: all twelve cases part from the oracle at such an iteration (cost equal
+# to the accepted cost to 1e-16) and then walk away from it, e.g. dense 3 x 40 clip5: stop 2/2/2, iterations 3/6/3, failures
+# 1/3/1 against the oracle's 5/2/2, 6/6/3, 4/3/1; the two device forms part from each other the same way.  These variants are
+# pinned by test_rejected_steps_roll_back_and_count instead: the oracle up to the tie, the rules of the loop body after it.
+# clip_total1 and clip_consec1 reject a step too, but their first rejection ends the solve — the step is rolled back, the StopReason
+# and the counters are set, and the restored point is never evaluated again: no tie, so they follow the oracle to the end (the
+# roll-back shows in the final x).
+_CLIPPED = ["clip5", "clip_total2", "clip_consec2", "clip_final_cost"]
+_FOLLOWED = [k for k in _VARIANTS if k not in _CLIPPED]
+_VARIANT_SCENES = [("dense", 3, 40), ("lists", 3, 40), ("lists", 12, 30)]
+_VREF = {}
+
+
+def _variant_ref(ta, oracle, ncam, npts, key):
+    """(data, x0, the oracle's solve) of the three scenes `synth_ba(3, C, N, float64, seed=9)` under one variant, once."""
+    k = (ncam, npts, key)
+    if k not in _VREF:
+        data, x0, _ = oracle.synth_ba(3, ncam, npts, np.float64, seed=9)
+        _VREF[k] = (data, x0, oracle.ba_lm(data, x0, ncam, npts, _variant(ta, key).to_pod()))
+    return _VREF[k]
+
+
+def _oracle_consec(ref):
+    """num_consec_failures is not among the oracle's outputs, but its history fixes it: the counter is zeroed by iteration 0 and by
+    every accepted step, and raised by every rejected step and every failed solve (optimizer.h:370-373, 441-453).  A stop below zero
+    ends an iteration before it is recorded.  Failed solves (num_failures minus the rejections on record) can be placed only when
+    there is no record at all, which is asserted."""
+    out = []
+    for p in range(len(ref["iters"])):
+        nh = int(ref["iters"][p]) - (1 if ref["stop"][p] < 0 else 0)
+        rejected = [i for i in range(1, nh) if not ref["succ"][p, i]]
+        solve_fails = int(ref["fails"][p]) - len(rejected)
+        assert solve_fails == 0 or nh == 0, (p, solve_fails, nh)
+        reset = max([i for i in range(nh) if i == 0 or ref["succ"][p, i]], default=-1)
+        out.append(len([i for i in rejected if i > reset]) + solve_fails)
+    return np.array(out)
+
+
+def _rolled_back(ref):
+    """Scenes whose record holds a rejected step right after an applied one: x (+)= -last_dx (optimizer.h:283-287)."""
+    return sum(1 for p in range(len(ref["iters"])) for i in range(1, int(ref["iters"][p]) if ref["stop"][p] >= 0 else 0)
+               if not ref["succ"][p, i] and (i == 1 or ref["succ"][p, i - 1]))
+
+
+def test_option_variants_reach_their_branches(ta, oracle):
+    """The oracle's own results on the inputs of test_option_variants_match_dense_oracle: at least one roll-back, one kMaxNoDecr,
+    one kMaxConsecNoDecr, one kSolverFailed after retries, scenes of one batch with different fates — so the pin cannot quietly
+    stop reaching those branches."""
+    SR = ta.StopReason
+    for ncam, npts in sorted({(c, n) for _, c, n in _VARIANT_SCENES}):
+        ref = {key: _variant_ref(ta, oracle, ncam, npts, key)[2] for key in _VARIANTS}
+        assert _rolled_back(ref["clip5"]) >= 1 and (ref["clip5"]["fails"] >= 1).all(), (ref["clip5"]["succ"], ref["clip5"]["fails"])
+        assert (ref["clip_total2"]["stop"] == int(SR.kMaxNoDecr)).any(), ref["clip_total2"]["stop"]
+        assert (ref["clip_consec2"]["stop"] == int(SR.kMaxConsecNoDecr)).any(), ref["clip_consec2"]["stop"]
+        assert (ref["clip_final_cost"]["fails"] >= 1).all(), ref["clip_final_cost"]["fails"]
+        assert (ref["min_h_diag"]["stop"] == int(SR.kSolverFailed)).all() and (ref["min_h_diag"]["iters"] == 1).all()
+        assert (ref["min_h_diag"]["fails"] == 5).all() and (_oracle_consec(ref["min_h_diag"]) == 5).all()
+        assert (ref["min_error"]["stop"] == int(SR.kMinError)).all() and (ref["min_error"]["iters"] == 1).all()
+        assert (ref["one_iter"]["stop"] == int(SR.kMaxIters)).all() and (ref["one_iter"]["iters"] == 2).all()
+        assert (ref["damping10"]["iters"] > ref["step_quality"]["iters"]).all(), (ref["damping10"]["iters"], ref["step_quality"]["iters"])
+        # the two variants that follow the oracle through a rejection: every scene rolls its only rejected step back and stops, and
+        # that step is far larger than x_tol, so a step left standing (or applied again) cannot pass the comparison of x
+        for key, stop in (("clip_total1", SR.kMaxNoDecr), ("clip_consec1", SR.kMaxConsecNoDecr)):
+            r = ref[key]
+            assert (r["stop"] == int(stop)).all() and (r["fails"] == 1).all() and (_oracle_consec(r) == 1).all(), (key, r["stop"], r["fails"])
+            assert _rolled_back(r) == 3, (key, r["succ"])
+            last = np.array([r["deltas2"][p, r["iters"][p] - 1] for p in range(3)])
+            assert (np.sqrt(last / (6 * ncam + 3 * npts)) > 100 * F64_TOL["x_tol"] * np.abs(r["x"]).max()).all(), (key, last)
+    r = _variant_ref(ta, oracle, 3, 40, "clip5")[2]
+    assert len(set(zip(r["stop"].tolist(), r["iters"].tolist(), r["fails"].tolist()))) == 3, (r["stop"], r["iters"], r["fails"])
+
+
+@pytest.mark.parametrize("key", _CLIPPED)
+@pytest.mark.parametrize("form,ncam,npts", _VARIANT_SCENES)
+def test_rejected_steps_roll_back_and_count(ta, oracle, form, ncam, npts, key):
+    """Rejected steps on the BA kernels, checked by what does not hang on a last bit (see _CLIPPED):
+      * up to the first iteration at which device and oracle part, the same costs (1e-9) and accept / reject flags; they part only
+        at an iteration that follows a rejected step and whose cost is the last accepted cost to 1e-11 on both sides: a proven tie;
+      * every rejected step that follows an applied one is rolled back: the next iteration's cost is the last accepted cost
+        to 1e-9 (a step applied a second time, or not taken back, leaves it percents away);
+      * the counters and the StopReason are those of optimizer.h:441-460 and :320-321 replayed on the device's OWN record: every
+        rejection counts, an accepted step zeroes the consecutive count, kMaxConsecNoDecr / kMaxNoDecr end the loop exactly when
+        their limit is reached, kMaxIters exactly at the iteration bound, and the final cost is the last accepted one."""
+    SR = ta.StopReason
+    data, x0, ref = _variant_ref(ta, oracle, ncam, npts, key)
+    opts = _variant(ta, key)
+    pod = opts.to_pod()
+    x, out = _run(ta, form, data, x0, ncam, npts, opts, np.float64)
+    got = gpu_dict(out, x)
+    consec = out.num_consec_failures.cpu().numpy()
+    print(f"REJECT {form} {ncam}x{npts} {key}: stop {got['stop']} / {ref['stop']}  iters {got['iters']} / {ref['iters']}  "
+          f"fails {got['fails']} / {ref['fails']}  consec {consec} / {_oracle_consec(ref)}")
+    bound = pod.max_iters + 1 + (1 if pod.check_final_cost else 0)
+    rolled = 0
+    for p in range(3):
+        e, s, k = got["errs"][p], got["succ"][p], int(got["iters"][p])
+        re_, rs, rk = ref["errs"][p], ref["succ"][p], int(ref["iters"][p])
+        label = (form, ncam, npts, key, p)
+        assert got["stop"][p] > 0 and 1 <= k <= bound, (label, got["stop"][p], k)
+        d = first_divergence(e, s, k, re_, rs, rk, rtol=1e-9, atol=1e-300)
+        if d is not None and d < min(k, rk):
+            acc = last_accepted(e, s, d)
+            assert d >= 2 and not s[d - 1] and not rs[d - 1], (label, "parted away from a roll-back", d)
+            assert abs(e[d] - acc) <= 1e-11 * acc and abs(re_[d] - acc) <= 1e-11 * acc, (label, "parted away from a tie", d, e[d], re_[d], acc)
+        fails = run = 0
+        stop = None
+        for i in range(k):
+            assert stop is None, (label, "went on after a failure limit", i)
+            if i == 0 or s[i]:
+                run = 0
+                continue
+            fails += 1
+            run += 1
+            if pod.max_consec_failures > 0 and run >= pod.max_consec_failures: stop = int(SR.kMaxConsecNoDecr)
+            elif pod.max_total_failures > 0 and fails >= pod.max_total_failures: stop = int(SR.kMaxNoDecr)
+            if (i == 1 or s[i - 1]) and i + 1 < k:
+                rolled += 1
+                acc = last_accepted(e, s, i)
+                assert abs(e[i + 1] - acc) <= 1e-9 * acc, (label, "not rolled back", i, e[i + 1], acc)
+        assert fails == got["fails"][p] and run == consec[p], (label, fails, got["fails"][p], run, consec[p])
+        if stop is not None:
+            assert got["stop"][p] == stop, (label, got["stop"][p], stop)
+        elif got["stop"][p] == int(SR.kMaxIters):
+            assert k == bound, (label, k, bound)
+        else:
+            assert int(SR.kMinError) <= got["stop"][p] <= int(SR.kMinGradNorm), (label, got["stop"][p])
+        assert got["cost"][p] == last_accepted(e, s, k), (label, got["cost"][p], last_accepted(e, s, k))
+    assert rolled >= 1, (form, ncam, npts, key, "no roll-back on the device")
+
+
+@pytest.mark.parametrize("key", _FOLLOWED)
+@pytest.mark.parametrize("form,ncam,npts", _VARIANT_SCENES)
+def test_option_variants_match_dense_oracle(ta, oracle, form, ncam, npts, key):
+    """The "solve failed: count, stop or re-damp and retry" branch and the loop body of OptimizeAcc (accept, roll back or first
+    step, eval-only iteration, rebuild, the counters) on the BA kernels, which state them outside one wavefront: `ba_schur_kernel`
+    (dense form) and `bl_step_kernel` (lists form: 3 cameras, and 12 — the workgroup LDL^T behind bl_schur).  Whole trajectories
+    against the oracle with the fp64 tolerances of test_ba_matches_dense_oracle, and the same StopReason, iteration, failure and
+    consecutive-failure counts."""
+    P = 3
+    data, x0, ref = _variant_ref(ta, oracle, ncam, npts, key)
+    opts = _variant(ta, key)
+    x, out = _run(ta, form, data, x0, ncam, npts, opts, np.float64)
+    got = gpu_dict(out, x)
+    consec = out.num_consec_failures.cpu().numpy()
+    print(f"VARIANT {form} {ncam}x{npts} {key}: stop {got['stop']} / {ref['stop']}  iters {got['iters']} / {ref['iters']}  "
+          f"fails {got['fails']} / {ref['fails']}  consec {consec} / {_oracle_consec(ref)}")
+    refd = {k: ref[k] for k in ("errs", "succ", "iters", "stop", "x", "cost", "fails", "deltas2")}
+    st = check_trajectories(got, refd, np.float64, opts.to_pod(), tol=F64_TOL, label=f"BA {form} {ncam}x{npts} {key}")
+    assert st["full"] + st["ties"] == P, st
+    assert np.array_equal(got["stop"], ref["stop"]) and np.array_equal(got["iters"], ref["iters"])
+    assert np.array_equal(got["fails"], ref["fails"]) and np.array_equal(consec, _oracle_consec(ref))

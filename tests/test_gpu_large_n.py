@@ -181,11 +181,12 @@ def test_large_n_covariance(ta, oracle):
     assert ok2.cpu().numpy().tolist() == [1, 0, 1]
 
 
-def test_large_n_option_variants(ta, oracle):
-    """Every option branch of the state machine (same list as test_gpu_dense_row.py::test_option_variants) through the
-    workgroup-per-problem kernel at n = 72, against the oracle."""
+@pytest.mark.parametrize("n", [72, 136])
+def test_large_n_option_variants(ta, oracle, n):
+    """Every option branch of the state machine (same list as test_gpu_dense_row.py::test_option_variants) against the oracle,
+    through the workgroup-per-problem kernel (n = 72) and through the launch-per-stage pipeline with `large_post_kernel` (n = 136)."""
     pyoracle = oracle
-    A, b, x0, xs = pyoracle.synth_dense_row(8, 72, 300, np.float64, seed=3)
+    A, b, x0, xs = pyoracle.synth_dense_row(8, n, 300, np.float64, seed=3)
     model = ta.DenseRowNatural(torch.from_numpy(A).cuda(), torch.from_numpy(b).cuda())
     variants = []
     o = ta.Options(); o.solver_type = ta.Options.GaussNewton; variants.append(o)

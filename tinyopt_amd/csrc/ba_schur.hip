@@ -1,6 +1,7 @@
 // Bundle adjustment with the points eliminated ("block-sparse / Schur"): C SE3 cameras x N 3-D points,
-// reprojection residuals, the SAME Levenberg-Marquardt state machine as every other path (LmState, lm_judge_core,
-// lm_good_step / lm_bad_step of lm_device.hpp).  The reference has no such path: it would run `Optimize(x, acc)` on the
+// reprojection residuals, the SAME Levenberg-Marquardt state machine as every other path (lm_device.hpp: LmState, lm_state_reset,
+// lm_solve_failed, lm_judge_core, lm_advance, lm_write_results, lm_add_counters — one thread per scene runs them, the kernels here
+// only apply the action that comes back).  The reference has no such path: it would run `Optimize(x, acc)` on the
 // full (6C + 3N)^2 system with a dense LDL^T, or Eigen's SimplicialLDLT on the sparse one (include/tinyopt/math.h:232-240,
 // 266-277; README.md:30,165-167 "sparse is slow") — which is what the oracle does (oracle/ba.hpp).  Here the block
 // structure of H = [[U, W], [W^T, V]] (U: 6x6 per camera, V: 3x3 per point, W: 6x3 per observation) is used:
@@ -701,45 +702,14 @@ __global__ void __launch_bounds__(256, TOA_BA_WGS) ba_schur_kernel(const BaParam
     __syncthreads();
     // ================= Step bookkeeping + the loop body of OptimizeAcc (optimizer.h:266-310, 370-399), one thread =================
     if (tid == 0) {
-      const unsigned max_tries = opt.max_consec_failures > 0 ? (opt.max_consec_failures > 1 ? opt.max_consec_failures : 1) : 255;
-      int rc;  // 0 step, 1 solver failed for good, 2 early stop, -1 retry (same iteration)
-      if (solved) {
-        rc = 0;
-      } else {
-        S.num_consec = (S.num_consec + 1) & 0xff;
-        S.num_failures = (S.num_failures + 1) & 0xff;
-        if (S.cost_nres == 0) { S.stop = TOA_STOP_SKIPPED; rc = 2; }
-        else if (isnan(S.cost_val) || isinf(S.cost_val)) { S.stop = TOA_STOP_NAN_OR_INF; rc = 2; }
-        else if (opt.max_consec_failures > 0 && S.num_consec >= unsigned(opt.max_consec_failures)) {
-          if (S.final_cost < double(NumLimits<T>::max())) S.stop = TOA_STOP_MAX_CONSEC_NO_DECR;
-          rc = 1;
-        } else {
-          lm_bad_step(S, opt);
-          rc = (S.num_consec <= max_tries) ? -1 : 1;
-        }
-      }
-      int action = 0, cont = 1;
+      const int rc = solved ? 0 : lm_solve_failed(S, opt);   // -1: retry, the same iteration
+      LmAdvance adv = {0, 1};
       if (rc >= 0) {
-        int status = 0;
-        if (rc == 1) S.stop = TOA_STOP_SOLVER_FAILED;
-        if (rc == 0) status = lm_judge_core<T>(S, opt, *L.res, p, double(d2s), opt.min_grad_norm2 > 0.0f ? double(g2s) : 0.0, true);
-        bool eval_only = false;
-        if (status & 1) {
-          action = 1; S.has_last_dx = 1; S.last_was_success = 1;
-          if (opt.check_final_cost && S.iter + 1 == S.max_iters) eval_only = true;
-        } else {
-          if (S.has_last_dx) { action = 2; S.has_last_dx = 0; }
-          else if (status & 2) { action = 1; S.has_last_dx = 1; }
-          eval_only = (S.last_was_success == 0);
-          S.last_was_success = 0;
-        }
-        if (is_lm) S.rebuild = eval_only ? 0 : 1;
-        S.num_iters = S.num_iters + 1;
-        S.iter = S.iter + 1;
-        cont = (S.stop == TOA_STOP_NONE && S.iter < S.max_iters) ? 1 : 0;
+        const int status = rc == 0 ? lm_judge_core<T>(S, opt, *L.res, p, double(d2s), opt.min_grad_norm2 > 0.0f ? double(g2s) : 0.0, true) : 0;
+        adv = lm_advance(S, opt, rc, status);
       }
-      flags[0] = cont;
-      flags[2] = action;
+      flags[0] = adv.cont;
+      flags[2] = adv.action;
     }
     __syncthreads();
     const int action = flags[2];
@@ -763,22 +733,8 @@ __global__ void __launch_bounds__(256, TOA_BA_WGS) ba_schur_kernel(const BaParam
   // ---- optimizer.h:313-327
   for (int i = tid; i < 12 * C; i += 256) X[i] = poses[i];
   if (tid == 0) {
-    const toa_results& res = *L.res;
-    if (S.stop == TOA_STOP_NONE && S.num_iters >= S.max_iters) S.stop = TOA_STOP_MAX_ITERS;
-    res.stop_reason[p] = S.stop;
-    res.num_iters[p] = S.num_iters;
-    res.final_cost[p] = S.final_cost;
-    if (res.num_failures) res.num_failures[p] = int(S.num_failures);
-    if (res.num_consec_failures) res.num_consec_failures[p] = int(S.num_consec);
-    if (res.final_num_residuals) res.final_num_residuals[p] = S.final_nres;
-    if (res.final_rerr_dec) res.final_rerr_dec[p] = S.final_rerr;
-    if (res.final_inlier_ratio) res.final_inlier_ratio[p] = S.final_nres > 0 ? float(S.final_ninl) / float(S.final_nres) : 1.0f;
-    if (prm->counters) {
-      atomicAdd(&prm->counters[0], S.acc_passes);
-      atomicAdd(&prm->counters[1], S.eval_passes);
-      atomicAdd(&prm->counters[2], S.solves);
-      atomicAdd(&prm->counters[3], 1ull);
-    }
+    lm_write_results(S, *L.res, p);
+    if (prm->counters) lm_add_counters(prm->counters, S, 1ull);
   }
 }
 
@@ -858,7 +814,8 @@ int toa_ba_launch_robust(toa_handle h, int dtype, BaParams& prm) {
 //                                      Cholesky up to 512 (fp64) / 1024 (fp32), rocSOLVER potrf beyond
 //   bl_back     thread / point         dp_j = -V_j^-1 (g_pj + sum W_ij^T dc), |dx|^2, |g|^2 partials
 //   bl_step     workgroup / scene      the rest of Step + the loop body of OptimizeAcc (optimizer.h:266-310, 370-539): the same
-//                                      scalar state machine as every other path (lm_judge_core, lm_good_step / lm_bad_step)
+//                                      scalar state machine as every other path (lm_solve_failed, lm_judge_core, lm_advance — which
+//                                      takes the host's timed_out —, lm_write_results)
 //   bl_update   thread / pose, point   x (+)= dx or the roll-back (sophus.h:24-26, traits.h:184-190)
 //
 // W_ij = J_c^T J_p is never stored: every site contracts through the 2-vector J_c dc / the 2 x 3 J_p instead (18 values
@@ -996,28 +953,14 @@ __global__ void __launch_bounds__(64) bl_init_kernel(const BlParams* __restrict_
   const BlIdx ix(prm->C, prm->N, prm->M);
   LmState<T>& S = *bl_state<T>(prm, wk, p);
   if (threadIdx.x == 0) {
-    const toa_options& opt = prm->opt;
-    S.lambda = opt.damping_init; S.prev_lambda = 0; S.bad_factor = opt.bad_factor; S.rebuild = 1;
-    S.final_cost = kDblMax; S.final_nres = 0; S.final_ninl = 0; S.cost_ninl = 0; S.final_rerr = kDblMax;
-    S.stop = TOA_STOP_NONE; S.num_iters = 0; S.num_failures = 0; S.num_consec = 0;
-    S.cost_val = 0; S.cost_nres = 0;
-    S.max_iters = opt.max_iters + 1 + (opt.check_final_cost ? 1 : 0);
-    S.has_last_dx = 0; S.last_was_success = 1; S.iter = 0;
+    lm_state_reset(S, prm->opt);
     S.acc_passes = 0; S.eval_passes = 0; S.solves = 0; S.problems = 0;
     int* fl = prm->iwork + size_t(p) * ix.total + ix.flags;
     fl[0] = 1; fl[1] = 1;
     if (fl[6]) {   // malformed observation list: nothing is optimised, the Output of an untouched problem with kSkipped
       S.stop = TOA_STOP_SKIPPED;
       fl[0] = 0;
-      const toa_results& res = prm->res;
-      res.stop_reason[p] = TOA_STOP_SKIPPED;
-      res.num_iters[p] = 0;
-      res.final_cost[p] = kDblMax;
-      if (res.num_failures) res.num_failures[p] = 0;
-      if (res.num_consec_failures) res.num_consec_failures[p] = 0;
-      if (res.final_num_residuals) res.final_num_residuals[p] = 0;
-      if (res.final_rerr_dec) res.final_rerr_dec[p] = kDblMax;
-      if (res.final_inlier_ratio) res.final_inlier_ratio[p] = 1.0f;
+      lm_write_results(S, prm->res, p);
       if (prm->counters) atomicAdd(&prm->counters[3], 1ull);
     }
   }
@@ -1612,65 +1555,19 @@ __global__ void __launch_bounds__(256) bl_step_kernel(const BlParams* __restrict
   __syncthreads();
   if (tid == 0) {
     if (fl[3]) S.solves++;
-    const unsigned max_tries = opt.max_consec_failures > 0 ? (opt.max_consec_failures > 1 ? opt.max_consec_failures : 1) : 255;
-    int rc;  // 0 step, 1 solver failed for good, 2 early stop, -1 retry (same iteration)
-    if (solved) {
-      rc = 0;
-    } else {
-      S.num_consec = (S.num_consec + 1) & 0xff;
-      S.num_failures = (S.num_failures + 1) & 0xff;
-      if (S.cost_nres == 0) { S.stop = TOA_STOP_SKIPPED; rc = 2; }
-      else if (isnan(S.cost_val) || isinf(S.cost_val)) { S.stop = TOA_STOP_NAN_OR_INF; rc = 2; }
-      else if (opt.max_consec_failures > 0 && S.num_consec >= unsigned(opt.max_consec_failures)) {
-        if (S.final_cost < double(NumLimits<T>::max())) S.stop = TOA_STOP_MAX_CONSEC_NO_DECR;
-        rc = 1;
-      } else {
-        lm_bad_step(S, opt);
-        rc = (S.num_consec <= max_tries) ? -1 : 1;
-      }
-    }
-    int action = 0, cont = 1;
+    const int rc = solved ? 0 : lm_solve_failed(S, opt);   // -1: retry, the same iteration
+    LmAdvance adv = {0, 1};
     if (rc >= 0) {
-      int status = 0;
-      if (rc == 1) S.stop = TOA_STOP_SOLVER_FAILED;
-      if (rc == 0) status = lm_judge_core<T>(S, opt, prm->res, p, double(d2s), opt.min_grad_norm2 > 0.0f ? double(g2s) : 0.0, true);
-      bool eval_only = false;
-      if (status & 1) {
-        action = 1; S.has_last_dx = 1; S.last_was_success = 1;
-        if (opt.check_final_cost && S.iter + 1 == S.max_iters) eval_only = true;
-      } else {
-        if (S.has_last_dx) { action = 2; S.has_last_dx = 0; }
-        else if (status & 2) { action = 1; S.has_last_dx = 1; }
-        eval_only = (S.last_was_success == 0);
-        S.last_was_success = 0;
-      }
-      if (is_lm) S.rebuild = eval_only ? 0 : 1;
-      if (timed_out && S.stop == TOA_STOP_NONE) S.stop = TOA_STOP_TIMED_OUT;   // optimizer.h:302-305 (after the step was applied)
-      S.num_iters = S.num_iters + 1;
-      S.iter = S.iter + 1;
-      cont = (S.stop == TOA_STOP_NONE && S.iter < S.max_iters) ? 1 : 0;
+      const int status = rc == 0 ? lm_judge_core<T>(S, opt, prm->res, p, double(d2s), opt.min_grad_norm2 > 0.0f ? double(g2s) : 0.0, true) : 0;
+      adv = lm_advance(S, opt, rc, status, timed_out != 0);
     }
     fl[1] = (!is_lm || S.rebuild) ? 1 : 0;
-    fl[2] = action;
-    fl[0] = cont;
-    if (cont) atomicAdd(any_active, 1);   // this pass's slot of the host's ring
-    if (!cont) {   // optimizer.h:313-327
-      const toa_results& res = prm->res;
-      if (S.stop == TOA_STOP_NONE && S.num_iters >= S.max_iters) S.stop = TOA_STOP_MAX_ITERS;
-      res.stop_reason[p] = S.stop;
-      res.num_iters[p] = S.num_iters;
-      res.final_cost[p] = S.final_cost;
-      if (res.num_failures) res.num_failures[p] = int(S.num_failures);
-      if (res.num_consec_failures) res.num_consec_failures[p] = int(S.num_consec);
-      if (res.final_num_residuals) res.final_num_residuals[p] = S.final_nres;
-      if (res.final_rerr_dec) res.final_rerr_dec[p] = S.final_rerr;
-      if (res.final_inlier_ratio) res.final_inlier_ratio[p] = S.final_nres > 0 ? float(S.final_ninl) / float(S.final_nres) : 1.0f;
-      if (prm->counters) {
-        atomicAdd(&prm->counters[0], S.acc_passes);
-        atomicAdd(&prm->counters[1], S.eval_passes);
-        atomicAdd(&prm->counters[2], S.solves);
-        atomicAdd(&prm->counters[3], 1ull);
-      }
+    fl[2] = adv.action;
+    fl[0] = adv.cont;
+    if (adv.cont) atomicAdd(any_active, 1);   // this pass's slot of the host's ring
+    if (!adv.cont) {   // optimizer.h:313-327
+      lm_write_results(S, prm->res, p);
+      if (prm->counters) lm_add_counters(prm->counters, S, 1ull);
     }
   }
 }
@@ -1713,23 +1610,10 @@ __global__ void __launch_bounds__(64) bl_force_stop_kernel(const BlParams* __res
   int* fl = prm->iwork + size_t(p) * ix.total + ix.flags;
   if (threadIdx.x != 0 || !fl[0]) return;
   LmState<T>& S = *bl_state<T>(prm, wk, p);
-  const toa_results& res = prm->res;
   fl[0] = 0;
-  if (S.stop == TOA_STOP_NONE) S.stop = TOA_STOP_MAX_ITERS;
-  res.stop_reason[p] = S.stop;
-  res.num_iters[p] = S.num_iters;
-  res.final_cost[p] = S.final_cost;
-  if (res.num_failures) res.num_failures[p] = int(S.num_failures);
-  if (res.num_consec_failures) res.num_consec_failures[p] = int(S.num_consec);
-  if (res.final_num_residuals) res.final_num_residuals[p] = S.final_nres;
-  if (res.final_rerr_dec) res.final_rerr_dec[p] = S.final_rerr;
-  if (res.final_inlier_ratio) res.final_inlier_ratio[p] = S.final_nres > 0 ? float(S.final_ninl) / float(S.final_nres) : 1.0f;
-  if (prm->counters) {
-    atomicAdd(&prm->counters[0], S.acc_passes);
-    atomicAdd(&prm->counters[1], S.eval_passes);
-    atomicAdd(&prm->counters[2], S.solves);
-    atomicAdd(&prm->counters[3], 1ull);
-  }
+  if (S.stop == TOA_STOP_NONE) S.stop = TOA_STOP_MAX_ITERS;   // whatever the iteration count: the HOST's budget ran out
+  lm_write_results(S, prm->res, p);
+  if (prm->counters) lm_add_counters(prm->counters, S, 1ull);
 }
 
 template <typename T>

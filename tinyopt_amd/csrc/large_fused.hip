@@ -4,7 +4,7 @@
 // Replaces, for this range of n, the launch-per-phase pipeline of large_n.hip (rows kernel writing J, rocBLAS
 // gemm_batched J^T J, pre / Cholesky / post kernels, two integers read back per pass).  Same reference code
 // (OptimizeAcc optimizer.h:242-327, Step :331-539, SolverLM::Build lm.h:59-120, SolverGN::Solve gn.h:150-171), same
-// state machine pieces (LmState, lm_judge_core, lm_good_step / lm_bad_step from lm_device.hpp).
+// state machine pieces (LmState, lm_state_reset, lm_solve_failed, lm_judge_core, lm_advance, lm_write_results from lm_device.hpp).
 //
 //   data pass   the m rows are split into 4 contiguous ranges, one per wavefront; each wave streams its rows ONCE from
 //               HBM in matrix-core operand order and accumulates the Gram of [J | r] for them: J^T J as NB (NB + 1) / 2
@@ -16,7 +16,8 @@
 //   Solve       blocked LDL^T of the LDS image by the four waves, trailing updates on the matrix cores, substitutions in
 //               wave 0 (ldlt_wg.hpp).  Acceptance differs from Eigen's LDLT only for singular positive SEMI-definite
 //               matrices, exactly like the library path.
-//   Step / loop thread 0 runs lm_judge_core and the loop bookkeeping; x, g, dx, last_dx live in LDS.
+//   Step / loop thread 0 runs lm_solve_failed / lm_judge_core / lm_advance with the memo bookkeeping around them and hands the
+//               action to the workgroup through LDS flags; x, g, dx, last_dx live in LDS.  The work counters are per workgroup.
 //
 // HBM traffic per LM iteration: m (n + 1) sizeof(T) — the algorithmic minimum (the library path: 3x that for J alone).
 #include <string>
@@ -367,15 +368,9 @@ __device__ __forceinline__ void large_fused_body(const LfArgs<T>& a) {
     if (p >= a.P) break;
     const T* A = a.data + size_t(p) * m * (size_t(n) + 1);
     const T* bv = A + size_t(m) * n;
-    if (tid == 0) {  // lm_init (lm.h:46-52, output.h:104-117, optimizer.h:248-250)
-      S.lambda = opt.damping_init; S.prev_lambda = 0; S.bad_factor = opt.bad_factor; S.rebuild = 1;
-      S.final_cost = kDblMax; S.final_nres = 0; S.final_ninl = 0; S.cost_ninl = 0; S.final_rerr = kDblMax;
-      S.stop = TOA_STOP_NONE; S.num_iters = 0; S.num_failures = 0; S.num_consec = 0;
-      S.cost_val = 0; S.cost_nres = 0;
-      S.max_iters = opt.max_iters + 1 + (opt.check_final_cost ? 1 : 0);
-      S.has_last_dx = 0; S.last_was_success = 1; S.iter = 0;
+    if (tid == 0) {
+      lm_state_reset(S, opt);
       S.acc_passes = S.eval_passes = S.solves = S.problems = 0;
-      S.acc_at_x = 0; S.memo_valid = 0; S.memo_hit = 0;
       sh_cur = 0; sh_memo_idx = 0; sh_park = 0; sh_check = 0;
     }
     for (int i = tid; i < NV; i += 256) {
@@ -559,61 +554,27 @@ __device__ __forceinline__ void large_fused_body(const LfArgs<T>& a) {
         solver_failed = bad > 0;
       }
       if (tid == 0) {
-        const unsigned max_tries = opt.max_consec_failures > 0 ? (opt.max_consec_failures > 1 ? opt.max_consec_failures : 1) : 255;
-        int rc;  // 0 step, 1 solver failed for good, 2 early stop, -1 retry (same iteration, next trip)
         if (built) n_solves++;
-        if (!solver_failed) {
-          rc = 0;
-        } else {  // optimizer.h:370-390
-          S.num_consec = (S.num_consec + 1) & 0xff;
-          S.num_failures = (S.num_failures + 1) & 0xff;
-          if (S.cost_nres == 0) { S.stop = TOA_STOP_SKIPPED; rc = 2; }
-          else if (isnan(S.cost_val) || isinf(S.cost_val)) { S.stop = TOA_STOP_NAN_OR_INF; rc = 2; }
-          else if (opt.max_consec_failures > 0 && S.num_consec >= unsigned(opt.max_consec_failures)) {
-            if (S.final_cost < double(NumLimits<T>::max())) S.stop = TOA_STOP_MAX_CONSEC_NO_DECR;
-            rc = 1;
-          } else {
-            lm_bad_step(S, opt);  // FailedStep == BadStep  lm.h:148
-            rc = (S.num_consec <= max_tries) ? -1 : 1;
-          }
-        }
-        int action = 0;  // 1: x += dx, last_dx = dx ; 2: x -= last_dx
-        int cont = 1;
-        int park = 0, check = 0;
+        const int rc = solver_failed ? lm_solve_failed(S, opt) : 0;   // -1: retry, the same iteration in the next trip
+        LmAdvance adv = {0, 1};
+        int park = 0;
         if (rc >= 0) {
-          int status = 0;
-          if (rc == 1) S.stop = TOA_STOP_SOLVER_FAILED;  // :396-399
-          if (rc == 0) status = lm_judge_core<T>(S, opt, res, p, dx_norm2, grad_norm2, true);
-          bool eval_only = false;  // optimizer.h:269-309
+          const int status = rc == 0 ? lm_judge_core<T>(S, opt, res, p, dx_norm2, grad_norm2, true) : 0;
           S.memo_hit = 0;           // (only the roll-back below may arm it, for the Build that follows directly)
-          if (status & 1) {
+          if (a.memo && (status & 1)) {
             // x is about to leave an ACCEPTED point: if the step that follows is rejected the loop comes back here and accumulates
             // again — park this point's linearisation (lm_device.hpp, lm_iteration).  An eval-only iteration that succeeds leaves
             // from a point whose linearisation was never formed: nothing to park.
-            if (a.memo) {
-              if (S.acc_at_x) { park = 1; S.memo_valid = 1; sh_memo_idx = sh_cur; memo_cost = lin_cost; memo_ninl = lin_ninl; }
-              else S.memo_valid = 0;
-            }
-            action = 1;
-            S.acc_at_x = 0;
-            S.has_last_dx = 1;
-            S.last_was_success = 1;
-            if (opt.check_final_cost && S.iter + 1 == S.max_iters) eval_only = true;
-          } else {
-            if (S.has_last_dx) { action = 2; S.has_last_dx = 0; S.acc_at_x = 0; check = (a.memo && S.memo_valid) ? 1 : 0; }
-            else if (status & 2) { action = 1; S.has_last_dx = 1; S.acc_at_x = 0; }
-            eval_only = (S.last_was_success == 0);
-            S.last_was_success = 0;
+            if (S.acc_at_x) { park = 1; S.memo_valid = 1; sh_memo_idx = sh_cur; memo_cost = lin_cost; memo_ninl = lin_ninl; }
+            else S.memo_valid = 0;
           }
-          if (is_lm) S.rebuild = eval_only ? 0 : 1;
-          S.num_iters = S.num_iters + 1;
-          S.iter = S.iter + 1;
-          cont = (S.stop == TOA_STOP_NONE && S.iter < S.max_iters) ? 1 : 0;
+          adv = lm_advance(S, opt, rc, status);
+          if (adv.action) S.acc_at_x = 0;   // x moves
         }
-        sh_action = action;
-        sh_cont = cont;
+        sh_action = adv.action;
+        sh_cont = adv.cont;
         sh_park = park;
-        sh_check = check;
+        sh_check = (adv.action == 2 && a.memo && S.memo_valid) ? 1 : 0;
       }
       __syncthreads();
       const int action = sh_action;
@@ -646,15 +607,7 @@ __device__ __forceinline__ void large_fused_body(const LfArgs<T>& a) {
       }
     }
     if (tid == 0) {
-      if (S.stop == TOA_STOP_NONE && S.num_iters >= S.max_iters) S.stop = TOA_STOP_MAX_ITERS;  // :320-321
-      res.stop_reason[p] = S.stop;
-      res.num_iters[p] = S.num_iters;
-      res.final_cost[p] = S.final_cost;
-      if (res.num_failures) res.num_failures[p] = int(S.num_failures);
-      if (res.num_consec_failures) res.num_consec_failures[p] = int(S.num_consec);
-      if (res.final_num_residuals) res.final_num_residuals[p] = S.final_nres;
-      if (res.final_rerr_dec) res.final_rerr_dec[p] = S.final_rerr;
-      if (res.final_inlier_ratio) res.final_inlier_ratio[p] = S.final_nres > 0 ? float(S.final_ninl) / float(S.final_nres) : 1.0f;
+      lm_write_results(S, res, p);
       n_problems++;
     }
     __syncthreads();  // Hs / LDS of this problem are free again

@@ -300,7 +300,8 @@ int large_inv_t(toa_handle h, RocApi& api, int n, int64_t P, const T* H, T* Cm, 
 
 // =====================================================================================================================
 // The LM / GN loop for n > 63 (TOA_MODEL_DENSE_ROW_NATURAL): same state machine as lm_device.hpp (its scalar pieces are
-// shared: LmState, lm_good_step / lm_bad_step, lm_judge_core), but the vectors of a problem live in HBM, one
+// shared: LmState, lm_state_reset, lm_solve_failed, lm_judge_core, lm_advance, lm_write_results / lm_write_running,
+// lm_add_counters; the memo bookkeeping is written around lm_advance in large_post_kernel), but the vectors of a problem live in HBM, one
 // WORKGROUP owns a problem inside the small kernels, and the two heavy operations are library calls:
 //   rows kernel   r_i, and J = diag(s) A written once (HBM-bound: reads m (n + 1), writes m n)
 //   rocBLAS       H = J^T J (gemm_strided_batched: at n >= 64 the residual block IS a real dense contraction),
@@ -399,16 +400,9 @@ __global__ void __launch_bounds__(256) large_init_kernel(const LargeArgs<T> a) {
   const long long p = blockIdx.x * 256ll + threadIdx.x;
   if (p >= a.P) return;
   LmState<T>& S = a.st[p];
-  const toa_options& opt = a.opt;
-  S.lambda = opt.damping_init; S.prev_lambda = 0; S.bad_factor = opt.bad_factor; S.rebuild = 1;  // lm.h:46-52
-  S.final_cost = kDblMax; S.final_nres = 0; S.final_ninl = 0; S.cost_ninl = 0; S.final_rerr = kDblMax;  // output.h:104-117
-  S.stop = TOA_STOP_NONE; S.num_iters = 0; S.num_failures = 0; S.num_consec = 0;
-  S.cost_val = 0; S.cost_nres = 0;
-  S.max_iters = opt.max_iters + 1 + (opt.check_final_cost ? 1 : 0);  // optimizer.h:248-250
-  S.has_last_dx = 0; S.last_was_success = 1; S.iter = 0;
+  lm_state_reset(S, a.opt);
   S.acc_passes = S.eval_passes = S.solves = S.problems = 0;
   S.reused_passes = 0;
-  S.acc_at_x = 0; S.memo_valid = 0; S.memo_hit = 0;
   a.active[p] = 1;
   a.built[p] = 0;
   if (a.skip) { a.skip[p] = 0; a.cur[p] = 0; a.midx[p] = 0; }
@@ -1804,21 +1798,10 @@ __device__ void large_finish_problem(const LargeArgs<T>& a, const long long p) {
     }
   }
   if (tid == 0) {
-    if (S.stop == TOA_STOP_NONE && S.num_iters >= S.max_iters) S.stop = TOA_STOP_MAX_ITERS;  // :320-321
-    res.stop_reason[p] = S.stop;
-    res.num_iters[p] = S.num_iters;
-    res.final_cost[p] = S.final_cost;
-    if (res.num_failures) res.num_failures[p] = int(S.num_failures);
-    if (res.num_consec_failures) res.num_consec_failures[p] = int(S.num_consec);
-    if (res.final_num_residuals) res.final_num_residuals[p] = S.final_nres;
-    if (res.final_rerr_dec) res.final_rerr_dec[p] = S.final_rerr;
-    if (res.final_inlier_ratio) res.final_inlier_ratio[p] = S.final_nres > 0 ? float(S.final_ninl) / float(S.final_nres) : 1.0f;
+    lm_write_results(S, res, p);
     a.active[p] = 0;
     if (a.counters) {
-      atomicAdd(&a.counters[0], S.acc_passes);
-      atomicAdd(&a.counters[1], S.eval_passes);
-      atomicAdd(&a.counters[2], S.solves);
-      atomicAdd(&a.counters[3], 1ull);
+      lm_add_counters(a.counters, S, 1ull);
       if (S.reused_passes) atomicAdd(&a.counters[4], S.reused_passes);
     }
   }
@@ -1858,61 +1841,27 @@ __global__ void __launch_bounds__(256) large_post_kernel(const LargeArgs<T> a, i
     solver_failed = bad > 0;
   }
   if (tid == 0) {
-    const unsigned max_tries = opt.max_consec_failures > 0 ? (opt.max_consec_failures > 1 ? opt.max_consec_failures : 1) : 255;
-    int rc;  // 0 step, 1 solver failed for good, 2 early stop, -1 retry (same iteration, next pass)
     if (built) S.solves++;
-    if (!solver_failed) {
-      rc = 0;
-    } else {  // optimizer.h:370-390
-      S.num_consec = (S.num_consec + 1) & 0xff;
-      S.num_failures = (S.num_failures + 1) & 0xff;
-      if (S.cost_nres == 0) { S.stop = TOA_STOP_SKIPPED; rc = 2; }
-      else if (isnan(S.cost_val) || isinf(S.cost_val)) { S.stop = TOA_STOP_NAN_OR_INF; rc = 2; }
-      else if (opt.max_consec_failures > 0 && S.num_consec >= unsigned(opt.max_consec_failures)) {
-        if (S.final_cost < double(NumLimits<T>::max())) S.stop = TOA_STOP_MAX_CONSEC_NO_DECR;
-        rc = 1;
-      } else {
-        lm_bad_step(S, opt);  // FailedStep == BadStep  lm.h:148
-        rc = (S.num_consec <= max_tries) ? -1 : 1;
-      }
-    }
-    int action = 0;  // 1: x += dx, last_dx = dx ; 2: x -= last_dx
-    int cont = 1;
-    int park = 0, check = 0;
+    const int rc = solver_failed ? lm_solve_failed(S, opt) : 0;   // -1: retry, the same iteration in the next pass
+    LmAdvance adv = {0, 1};
+    int park = 0;
     if (rc >= 0) {
-      int status = 0;
-      if (rc == 1) S.stop = TOA_STOP_SOLVER_FAILED;  // :396-399
-      if (rc == 0) status = lm_judge_core<T>(S, opt, res, p, dx_norm2, grad_norm2, true);
-      bool eval_only = false;  // optimizer.h:269-309
+      const int status = rc == 0 ? lm_judge_core<T>(S, opt, res, p, dx_norm2, grad_norm2, true) : 0;
       S.memo_hit = 0;           // (only the roll-back below may arm it, for the Build that follows directly)
-      if (status & 1) {
+      if (memo && (status & 1)) {
         // x is about to leave an ACCEPTED point: park its linearisation (the slot it lives in simply becomes the memo's) — unless
         // it was never formed (an eval-only iteration that succeeded): lm_device.hpp, lm_iteration
-        if (memo) {
-          if (S.acc_at_x) { park = 1; S.memo_valid = 1; a.midx[p] = a.cur[p]; a.memo_cost[p] = a.lin_cost[p]; a.memo_ninl[p] = a.lin_ninl[p]; }
-          else S.memo_valid = 0;
-        }
-        action = 1;
-        S.acc_at_x = 0;
-        S.has_last_dx = 1;
-        S.last_was_success = 1;
-        if (opt.check_final_cost && S.iter + 1 == S.max_iters) eval_only = true;
-      } else {
-        if (S.has_last_dx) { action = 2; S.has_last_dx = 0; S.acc_at_x = 0; check = (memo && S.memo_valid) ? 1 : 0; }
-        else if (status & 2) { action = 1; S.has_last_dx = 1; S.acc_at_x = 0; }
-        eval_only = (S.last_was_success == 0);
-        S.last_was_success = 0;
+        if (S.acc_at_x) { park = 1; S.memo_valid = 1; a.midx[p] = a.cur[p]; a.memo_cost[p] = a.lin_cost[p]; a.memo_ninl[p] = a.lin_ninl[p]; }
+        else S.memo_valid = 0;
       }
-      if (opt.solver_type == 0) S.rebuild = eval_only ? 0 : 1;
-      S.num_iters = S.num_iters + 1;
-      S.iter = S.iter + 1;
-      cont = (S.stop == TOA_STOP_NONE && S.iter < S.max_iters) ? 1 : 0;
+      adv = lm_advance(S, opt, rc, status);
+      if (adv.action) S.acc_at_x = 0;   // x moves
     }
-    sh_action = action;
-    sh_cont = cont;
+    sh_action = adv.action;
+    sh_cont = adv.cont;
     sh_retry = rc < 0 ? 1 : 0;
     sh_park = park;
-    sh_check = check;
+    sh_check = (adv.action == 2 && memo && S.memo_valid) ? 1 : 0;
   }
   __syncthreads();
   const int action = sh_action;
@@ -1946,11 +1895,7 @@ __global__ void __launch_bounds__(256) large_post_kernel(const LargeArgs<T> a, i
         if (retry) atomicAdd(&summary[2], 1);
         else {
           a.stepped[p] = 1;   // (every thread read on(p) before the barrier above)
-          res.stop_reason[p] = TOA_STOP_NONE;   // running: the results so far (toa_lm_step's contract)
-          res.num_iters[p] = S.num_iters;
-          res.final_cost[p] = S.final_cost;
-          if (res.num_failures) res.num_failures[p] = int(S.num_failures);
-          if (res.num_consec_failures) res.num_consec_failures[p] = int(S.num_consec);
+          lm_write_running(S, res, p);
           if (a.active_out) atomicAdd(a.active_out, 1);
         }
       }

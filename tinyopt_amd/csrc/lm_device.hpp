@@ -182,6 +182,30 @@ __device__ __forceinline__ void lm_good_step(LmState<T>& S, const toa_options& o
   S.bad_factor = o.bad_factor;
 }
 
+// ---- The scalar pieces of Step and OptimizeAcc that every kernel family runs the same way — lm_solve_failed here, lm_judge_core,
+//      lm_state_reset, lm_advance, lm_write_results, lm_write_running and lm_add_counters below.  The kernels that keep a problem
+//      outside one wave (large_n.hip, large_fused.hip, ba_schur.hip) call them from one thread and broadcast what comes back.  Of
+//      the one-wavefront functions below only lm_init calls one (lm_state_reset): lm_build_and_solve's tail, lm_iteration and
+//      lm_finalize state the same rules wave-uniformly in their own text, because routing them through these functions changes
+//      the register allocation of lm_fused_kernel (measured per kernel: VGPRs and SGPR spills move), which sits at its limits.
+
+// A Build or Solve failed (optimizer.h:370-390): count it, then 2 = stopped early (no residuals, NaN / Inf cost), 1 = failed for
+// good (the consecutive limit, or the bound of the retry loop at :358), -1 = re-damped: Build again in the SAME iteration.
+template <typename T>
+__device__ __forceinline__ int lm_solve_failed(LmState<T>& S, const toa_options& opt) {
+  S.num_consec = (S.num_consec + 1) & 0xff;
+  S.num_failures = (S.num_failures + 1) & 0xff;
+  if (S.cost_nres == 0) { S.stop = TOA_STOP_SKIPPED; return 2; }
+  if (isnan(S.cost_val) || isinf(S.cost_val)) { S.stop = TOA_STOP_NAN_OR_INF; return 2; }
+  if (opt.max_consec_failures > 0 && S.num_consec >= unsigned(opt.max_consec_failures)) {
+    if (S.final_cost < double(NumLimits<T>::max())) S.stop = TOA_STOP_MAX_CONSEC_NO_DECR;
+    return 1;
+  }
+  lm_bad_step(S, opt);  // FailedStep == BadStep  lm.h:148
+  const unsigned max_tries = opt.max_consec_failures > 0 ? (opt.max_consec_failures > 1 ? opt.max_consec_failures : 1) : 255;
+  return S.num_consec <= max_tries ? -1 : 1;
+}
+
 // ---- Build (lm.h:59-120 / gn.h:117-147) + Solve (gn.h:150-171) with the retry loop of
 //      Step (optimizer.h:354-399).  Returns 0 = got a step (in L.dx), 1 = solver failed for good
 //      (stop may or may not be set), 2 = early return with stop set.
@@ -363,24 +387,92 @@ __device__ __forceinline__ int lm_judge_step(WaveLds<T>& L, const int n, const i
   return lm_judge_core<T>(S, opt, *L.res, p, dx_norm2, grad_norm2, lane == 0);
 }
 
+// SolverLM::reset (lm.h:46-52), Output's defaults (output.h:104-117) and the locals of OptimizeAcc (optimizer.h:248-263): every
+// scalar a solve starts from.  The work counters and what a kernel family keeps beside the record stay with the caller.
+template <typename T>
+__device__ __forceinline__ void lm_state_reset(LmState<T>& S, const toa_options& opt) {
+  S.lambda = opt.damping_init; S.prev_lambda = 0; S.bad_factor = opt.bad_factor; S.rebuild = 1;
+  S.final_cost = kDblMax; S.final_nres = 0; S.final_ninl = 0; S.cost_ninl = 0; S.final_rerr = kDblMax;
+  S.stop = TOA_STOP_NONE; S.num_iters = 0; S.num_failures = 0; S.num_consec = 0;
+  S.cost_val = 0; S.cost_nres = 0;
+  S.max_iters = opt.max_iters + 1 + (opt.check_final_cost ? 1 : 0);
+  S.has_last_dx = 0; S.last_was_success = 1;
+  S.iter = 0;
+  S.acc_at_x = 0; S.memo_valid = 0; S.memo_hit = 0;
+}
+
+// What the loop body of OptimizeAcc (optimizer.h:269-309) does after Step, for the kernels that apply the step outside the thread
+// that decides.  rc: 0 = Step judged a step (`status` from lm_judge_core: bit0 good, bit1 has dx), 1 = the solve failed for good
+// (kSolverFailed, :396-399 — overwrites a kMaxConsecNoDecr set by lm_solve_failed), 2 = stopped early.  `timed_out`: the host's
+// clock has run out (:302-305) — it takes effect after the step is chosen and before the counters advance, as there.
+struct LmAdvance {
+  int action;  // 0 = x stays, 1 = x (+)= dx and last_dx = dx, 2 = roll back: x (+)= -last_dx
+  int cont;    // the loop goes on (:309 and the bound at :266)
+};
+template <typename T>
+__device__ __forceinline__ LmAdvance lm_advance(LmState<T>& S, const toa_options& opt, const int rc, const int status,
+                                                const bool timed_out = false) {
+  LmAdvance r;
+  r.action = 0;
+  if (rc == 1) S.stop = TOA_STOP_SOLVER_FAILED;
+  bool eval_only = false;
+  if (status & 1) {  // :271-279
+    r.action = 1; S.has_last_dx = 1; S.last_was_success = 1;
+    if (opt.check_final_cost && S.iter + 1 == S.max_iters) eval_only = true;
+  } else {           // :281-297
+    if (S.has_last_dx) { r.action = 2; S.has_last_dx = 0; }
+    else if (status & 2) { r.action = 1; S.has_last_dx = 1; }
+    eval_only = (S.last_was_success == 0);
+    S.last_was_success = 0;
+  }
+  if (opt.solver_type == 0) S.rebuild = eval_only ? 0 : 1;  // :299, lm.h:55 (GN: base.h:56 no-op)
+  if (timed_out && S.stop == TOA_STOP_NONE) S.stop = TOA_STOP_TIMED_OUT;
+  S.num_iters = S.num_iters + 1;                            // :307
+  S.iter = S.iter + 1;
+  r.cont = (S.stop == TOA_STOP_NONE && S.iter < S.max_iters) ? 1 : 0;
+  return r;
+}
+
+// The results row of a problem that is done (optimizer.h:320-327), by one thread.
+template <typename T>
+__device__ __forceinline__ void lm_write_results(LmState<T>& S, const toa_results& res, const long long p) {
+  if (S.stop == TOA_STOP_NONE && S.num_iters >= S.max_iters) S.stop = TOA_STOP_MAX_ITERS;  // :320-321
+  res.stop_reason[p] = S.stop;
+  res.num_iters[p] = S.num_iters;
+  res.final_cost[p] = S.final_cost;
+  if (res.num_failures) res.num_failures[p] = int(S.num_failures);
+  if (res.num_consec_failures) res.num_consec_failures[p] = int(S.num_consec);
+  if (res.final_num_residuals) res.final_num_residuals[p] = S.final_nres;
+  if (res.final_rerr_dec) res.final_rerr_dec[p] = S.final_rerr;
+  if (res.final_inlier_ratio) res.final_inlier_ratio[p] = S.final_nres > 0 ? float(S.final_ninl) / float(S.final_nres) : 1.0f;
+}
+
+// The row of a problem that is still running after an iteration of the stepping form (toa_lm_step's contract): StopReason kNone,
+// the iteration count, the last accepted cost and both failure counters so far; the other fields are written when it stops.
+template <typename T>
+__device__ __forceinline__ void lm_write_running(const LmState<T>& S, const toa_results& res, const long long p) {
+  res.stop_reason[p] = TOA_STOP_NONE;
+  res.num_iters[p] = S.num_iters;
+  res.final_cost[p] = S.final_cost;
+  if (res.num_failures) res.num_failures[p] = int(S.num_failures);
+  if (res.num_consec_failures) res.num_consec_failures[p] = int(S.num_consec);
+}
+
+// The work of finished problems into the batch counters (passes, cost-only passes, solves, problems), by one thread.
+template <typename T>
+__device__ __forceinline__ void lm_add_counters(unsigned long long* counters, const LmState<T>& S, const unsigned long long problems) {
+  atomicAdd(&counters[0], S.acc_passes);
+  atomicAdd(&counters[1], S.eval_passes);
+  atomicAdd(&counters[2], S.solves);
+  atomicAdd(&counters[3], problems);
+}
+
 // ---- the three stages of OptimizeAcc (optimizer.h:242-327), separable so that the same state machine runs either
 //      inside one wave for a whole solve (lm_solve_problem) or one iteration per launch with the state parked in
 //      global memory between launches (the row-split "wide" path for single huge problems, kernels.hpp).
 template <typename T>
 __device__ __forceinline__ void lm_init(WaveLds<T>& L, const int lane) {
-  LmState<T>& S = *L.st;
-  const toa_options& opt = *L.opt;
-  // SolverLM::reset  lm.h:46-52
-  S.lambda = opt.damping_init; S.prev_lambda = 0; S.bad_factor = opt.bad_factor; S.rebuild = 1;
-  // Output  output.h:104-117
-  S.final_cost = kDblMax; S.final_nres = 0; S.final_ninl = 0; S.cost_ninl = 0; S.final_rerr = kDblMax;
-  S.stop = TOA_STOP_NONE; S.num_iters = 0; S.num_failures = 0; S.num_consec = 0;
-  S.cost_val = 0; S.cost_nres = 0;
-  // OptimizeAcc locals  optimizer.h:248-263
-  S.max_iters = opt.max_iters + 1 + (opt.check_final_cost ? 1 : 0);
-  S.has_last_dx = 0; S.last_was_success = 1;
-  S.iter = 0;
-  S.acc_at_x = 0; S.memo_valid = 0; S.memo_hit = 0;
+  lm_state_reset(*L.st, *L.opt);
   L.ldx[lane] = T(0);
   L.dx[lane] = T(0);
   wave_sync();

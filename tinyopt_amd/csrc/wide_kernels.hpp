@@ -239,9 +239,7 @@ __global__ void __launch_bounds__(256) wide_step_kernel(const WideParams* __rest
     T* X = static_cast<T*>(prm->x);
     if (lane < xd) X[size_t(p) * xd + lane] = L.xs[lane];
     if (lane == 0) {
-      prm->res.num_iters[p] = L.st->num_iters;
-      prm->res.final_cost[p] = L.st->final_cost;
-      prm->res.stop_reason[p] = TOA_STOP_NONE;
+      lm_write_running(*L.st, prm->res, p);
       if (prm->active) atomicAdd(prm->active, 1);
     }
   }
@@ -250,12 +248,7 @@ __global__ void __launch_bounds__(256) wide_step_kernel(const WideParams* __rest
     const int xd = Manifold::kXdim ? Manifold::kXdim : n;
     T* X = static_cast<T*>(prm->x);
     if (lane < xd) X[size_t(p) * xd + lane] = L.xs[lane];
-    if (prm->counters && lane == 0) {
-      atomicAdd(&prm->counters[0], L.st->acc_passes);
-      atomicAdd(&prm->counters[1], L.st->eval_passes);
-      atomicAdd(&prm->counters[2], L.st->solves);
-      atomicAdd(&prm->counters[3], L.st->problems);
-    }
+    if (prm->counters && lane == 0) lm_add_counters(prm->counters, *L.st, L.st->problems);
   }
   wide_store_state(L, ws, lane);
 }
@@ -289,12 +282,7 @@ __global__ void __launch_bounds__(256) wide_stop_kernel(const WideParams* __rest
   L.st->stop = req;
   wave_sync();
   lm_finalize<T>(model, L, n, lane, p);
-  if (prm->counters && lane == 0) {
-    atomicAdd(&prm->counters[0], L.st->acc_passes);
-    atomicAdd(&prm->counters[1], L.st->eval_passes);
-    atomicAdd(&prm->counters[2], L.st->solves);
-    atomicAdd(&prm->counters[3], L.st->problems);
-  }
+  if (prm->counters && lane == 0) lm_add_counters(prm->counters, *L.st, L.st->problems);
   wide_store_state(L, ws, lane);
 }
 
@@ -442,12 +430,7 @@ __global__ void __launch_bounds__(512) wide_team_kernel(const WideParams* __rest
         lm_finalize<T>(fold, L, n, lane, p);
         T* X = static_cast<T*>(prm->x);
         if (lane < xd) X[size_t(p) * xd + lane] = L.xs[lane];
-        if (prm->counters && lane == 0) {
-          atomicAdd(&prm->counters[0], L.st->acc_passes);
-          atomicAdd(&prm->counters[1], L.st->eval_passes);
-          atomicAdd(&prm->counters[2], L.st->solves);
-          atomicAdd(&prm->counters[3], L.st->problems);
-        }
+        if (prm->counters && lane == 0) lm_add_counters(prm->counters, *L.st, L.st->problems);
       }
       xshare[lane] = L.xs[lane];
       if (lane == 0) { flags[0] = more ? 0 : 1; flags[1] = L.st->rebuild; }
@@ -560,12 +543,7 @@ __global__ void __launch_bounds__(64) wide_persistent_kernel(const WideParams* _
       lm_finalize<T>(fold, L, n, lane, p);
       T* X = static_cast<T*>(prm->x);
       if (lane < xd) X[size_t(p) * xd + lane] = L.xs[lane];
-      if (prm->counters && lane == 0) {
-        atomicAdd(&prm->counters[0], L.st->acc_passes);
-        atomicAdd(&prm->counters[1], L.st->eval_passes);
-        atomicAdd(&prm->counters[2], L.st->solves);
-        atomicAdd(&prm->counters[3], L.st->problems);
-      }
+      if (prm->counters && lane == 0) lm_add_counters(prm->counters, *L.st, L.st->problems);
     }
     publish(more ? TOA_STOP_NONE : (L.st->stop != TOA_STOP_NONE ? L.st->stop : TOA_STOP_MAX_ITERS));
     if (lane == 0) __hip_atomic_store(go, gen + 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);

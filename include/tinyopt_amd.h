@@ -705,6 +705,41 @@ int toa_jit_accumulate_ragged_prior(toa_handle h, toa_jit_model model, const int
                                     int64_t total_items, int64_t P, const void* data_dev, const void* x_dev, const toa_prior* prior, int want_grad,
                                     void* g_dev, void* H_dev, double* cost_dev, int32_t* nres_dev);
 int toa_jit_model_stats_prior(toa_handle h, toa_jit_model m, int ragged, int* wg_per_cu, int* num_regs, int* scratch_bytes);
+/*      Box bounds and fixed parameters for a run-time model: per problem, with n = num_params and in the model's
+ *      scalar type, lo_dev [P][n] and hi_dev [P][n]; -inf / +inf: no bound, lo_j == hi_j: parameter j is fixed.  Precondition (not
+ *      checked here, no host read): no NaN, lo <= hi.
+ *        1. Before the first Build x_j <- min(max(x_j, lo_j), hi_j); every x the solve visits and returns satisfies lo <= x <= hi
+ *           exactly, after a roll-back too.
+ *        2. After every Build (items, then the prior) parameter j is ACTIVE when lo_j == hi_j, or x_j <= lo_j and g_j > 0, or
+ *           x_j >= hi_j and g_j < 0 (g = J^T r).  For an active j: g_j = 0, row and column j of H are 0, H_jj = 1 — on the undamped
+ *           system, before grad_clipping, check_min_H_diag and the damping: dx_j = 0, and min_grad_norm2 tests the projected gradient.
+ *           Cost, residual count, inliers, the M-estimator and cost-only Evaluates are untouched.  A parameter leaves its bound as soon
+ *           as the gradient points inward.
+ *        3. x_j <- clip(x_j + dx_j); a clipped component's dx_j becomes the step taken, so that the roll-back (which clips too) undoes
+ *           it.  |dx|^2 of the stop test and of the history is the solver's step before clipping.
+ *      final_hessian is the matrix of the last Build: rows and columns of active parameters are unit vectors, so toa_inv_cov gives the
+ *      inverse of the free block for the free parameters and 1 on the active diagonal.  This is clip-and-reject, not a trust-region
+ *      reflection: with a small max_consec_failures a solve can stop with TOA_STOP_MAX_CONSEC_NO_DECR short of the constrained optimum.
+ *      prior: NULL for none.  toa_jit_accumulate_*_bounds take x as given and apply rule 2 to the g and H they write.  Each call mirrors
+ *      its twin without bounds (the same checks in the same order, then the bounds'; P == 0 returns TOA_OK; stream-ordered, no host
+ *      read) and always takes the one-launch form (never the row-split).  TOA_E_UNSUPPORTED: a model on TOA_MANIFOLD_SE3 /
+ *      TOA_MANIFOLD_USER, a scalar cost model, a large_n model.  TOA_E_ARG: a NULL bounds / lo_dev / hi_dev, pointers of another
+ *      device.  The kernels are one more code object per model, per form (uniform / ragged, with / without a prior) and per M-estimator
+ *      variant, built on first use and cached on disk; that first call is refused under stream capture.
+ *      toa_jit_model_stats_bounds: toa_jit_model_stats_ragged of the bounds fused kernel (plain L2) in the form named by ragged / with_prior. */
+typedef struct toa_bounds { const void* lo_dev; const void* hi_dev; int32_t reserved[4]; } toa_bounds;
+int toa_jit_lm_run_bounds(toa_handle h, toa_jit_model model, int num_items, int64_t P, const void* data_dev, void* x_dev, const toa_bounds* bounds,
+                          const toa_prior* prior, const toa_options* options, const toa_results* results, uint64_t* counters_dev);
+int toa_jit_lm_run_ragged_bounds(toa_handle h, toa_jit_model model, const int64_t* item_offsets_dev, const void* header_dev, int max_items,
+                                 int64_t total_items, int64_t P, const void* data_dev, void* x_dev, const toa_bounds* bounds, const toa_prior* prior,
+                                 const toa_options* options, const toa_results* results, uint64_t* counters_dev, uint32_t flags);
+int toa_jit_accumulate_bounds(toa_handle h, toa_jit_model model, int num_items, int64_t P, const void* data_dev, const void* x_dev,
+                              const toa_bounds* bounds, const toa_prior* prior, int want_grad, void* g_dev, void* H_dev, double* cost_dev,
+                              int32_t* nres_dev);
+int toa_jit_accumulate_ragged_bounds(toa_handle h, toa_jit_model model, const int64_t* item_offsets_dev, const void* header_dev, int max_items,
+                                     int64_t total_items, int64_t P, const void* data_dev, const void* x_dev, const toa_bounds* bounds,
+                                     const toa_prior* prior, int want_grad, void* g_dev, void* H_dev, double* cost_dev, int32_t* nres_dev);
+int toa_jit_model_stats_bounds(toa_handle h, toa_jit_model m, int ragged, int with_prior, int* wg_per_cu, int* num_regs, int* scratch_bytes);
 
 /* ---- C1: the result gather of a sharded batch (SURVEY §8(b) export list `gather(handle_group...)`, §8(e)).
  *      Problems are independent (the reference optimises exactly one x per call, docs/API.md:12), so a batch of P_total

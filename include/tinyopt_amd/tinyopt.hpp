@@ -23,6 +23,7 @@
 #include <cstdint>
 #include <functional>
 #include <iostream>
+#include <limits>
 #include <stdexcept>
 #include <string>
 #include <algorithm>
@@ -364,7 +365,7 @@ class JitResidual {
   //   diff/num_diff.h: the body runs on plain Scalar only.  Euclidean; no stop callbacks / max_duration_ms / log line.
   // large_n = true: the model is compiled for the launch-per-phase pipeline of the wide problems instead of a wavefront per problem —
   //   n up to 1024 (float) / 512 (double), item_scalars up to 2048; TOA_JIT_RESIDUAL / TOA_JIT_ACCUMULATE, Euclidean, TOA_DIFF_DEFAULT.
-  //   Optimize (LM / GN), Accumulate and diff::Eval / CalculateJac take it; with_loss, with_prior, bind_ragged, splits, the stepping
+  //   Optimize (LM / GN), Accumulate and diff::Eval / CalculateJac take it; with_loss, with_prior, with_bounds, bind_ragged, splits, the stepping
   //   Optimizer, host controls, GradientDescent and diff::CheckGradient are refused (std::invalid_argument).  Without it n = 64 is refused.
   JitResidual(const Context& ctx, const std::string& body, int n, int item_scalars, int residuals_per_item = 1, int header_scalars = 0,
               int manifold = TOA_MANIFOLD_EUCLID, int kind = TOA_JIT_RESIDUAL, const std::string& plus_body = std::string(), int x_scalars = 0,
@@ -463,9 +464,57 @@ class PriorTag {
   DeviceBuffer<Scalar> prior_mu_, prior_W_;
   int prior_rows_ = -1;   // -1: no prior
 };
+// Box bounds and fixed parameters of a bound run-time model (toa_jit_*_bounds): per problem lo <= x <= hi, [P][n]
+// host scalars each; nullptr for a side: no bound there (-inf / +inf); lo == hi holds a parameter constant.  x0 is clipped into the
+// box, after every Build the parameters on a bound with the gradient pointing outward (and the fixed ones) leave the system (g_j = 0,
+// row and column j of H zero, H_jj = 1), every step is clipped: every x visited and returned is inside the box exactly.
+// final_hessian is the projected matrix of the last Build (Covariance: the inverse of the free block, 1 on the active diagonal).
+// Clip-and-reject, not a trust-region reflection: a small max_consec_failures can stop a solve short of the constrained optimum.
+// Euclidean residual models, the one-launch form only: no host controls, no stepping Optimizer, no diff::Eval / CalculateJac /
+// CheckGradient.  Composes with with_loss and with_prior in any order.
 template <typename Scalar>
-class JitModel : public LossTag, public PriorTag<Scalar> {
+class BoundsTag {
  public:
+  bool has_bounds() const { return has_bounds_; }
+  toa_bounds bounds_pod() const {
+    toa_bounds b{};
+    b.lo_dev = lo_.data(); b.hi_dev = hi_.data();
+    return b;
+  }
+
+ protected:
+  void set_bounds(const JitResidual<Scalar>& res, int64_t P, const Scalar* lo, const Scalar* hi) {
+    if (res.large_n())
+      throw std::invalid_argument("tinyopt_amd::with_bounds: a model compiled with large_n takes no box bounds");
+    if (res.kind() == TOA_JIT_COST || res.kind() == TOA_JIT_COST_GRAD)
+      throw std::invalid_argument("tinyopt_amd::with_bounds: a scalar cost model has no Gauss-Newton system to project");
+    if (res.manifold() != TOA_MANIFOLD_EUCLID)
+      throw std::invalid_argument("tinyopt_amd::with_bounds: a box on the tangent is not a box on the parameter: Euclidean parameters only");
+    const size_t count = size_t(P) * size_t(res.n());
+    const Scalar inf = std::numeric_limits<Scalar>::infinity();
+    std::vector<Scalar> l(count, -inf), h(count, inf);
+    if (lo) l.assign(lo, lo + count);
+    if (hi) h.assign(hi, hi + count);
+    for (size_t i = 0; i < count; ++i)
+      if (!(l[i] <= h[i])) throw std::invalid_argument("tinyopt_amd::with_bounds: lo <= hi must hold for every parameter of every problem, without NaN");
+    lo_ = DeviceBuffer<Scalar>(res.ctx(), std::max<size_t>(1, count));
+    hi_ = DeviceBuffer<Scalar>(res.ctx(), std::max<size_t>(1, count));
+    if (count > 0) {
+      check(toa_memcpy_h2d(res.ctx().get(), lo_.data(), l.data(), count * sizeof(Scalar)));
+      check(toa_memcpy_h2d(res.ctx().get(), hi_.data(), h.data(), count * sizeof(Scalar)));
+    }
+    has_bounds_ = true;
+  }
+
+ private:
+  DeviceBuffer<Scalar> lo_, hi_;
+  bool has_bounds_ = false;
+};
+template <typename Scalar>
+class JitModel : public LossTag, public PriorTag<Scalar>, public BoundsTag<Scalar> {
+ public:
+  JitModel& with_bounds(const Scalar* lo, const Scalar* hi) & { this->set_bounds(*res_, P_, lo, hi); return *this; }
+  JitModel&& with_bounds(const Scalar* lo, const Scalar* hi) && { this->set_bounds(*res_, P_, lo, hi); return std::move(*this); }
   JitModel& with_prior(const Scalar* mu, const Scalar* W, int rows = 0) & { this->set_prior(*res_, P_, mu, W, rows); return *this; }
   JitModel&& with_prior(const Scalar* mu, const Scalar* W, int rows = 0) && { this->set_prior(*res_, P_, mu, W, rows); return std::move(*this); }
   JitModel(const JitResidual<Scalar>& res, int64_t P, int items, const Scalar* host)
@@ -493,8 +542,10 @@ class JitModel : public LossTag, public PriorTag<Scalar> {
 // and diff::CalculateJac, whose outputs are concatenated like the items.  One-launch form only: no host controls (stop callbacks,
 // max_duration_ms, the log line), no stepping Optimizer, no diff::CheckGradient.
 template <typename Scalar>
-class RaggedJitModel : public LossTag, public PriorTag<Scalar> {
+class RaggedJitModel : public LossTag, public PriorTag<Scalar>, public BoundsTag<Scalar> {
  public:
+  RaggedJitModel& with_bounds(const Scalar* lo, const Scalar* hi) & { this->set_bounds(*res_, P_, lo, hi); return *this; }
+  RaggedJitModel&& with_bounds(const Scalar* lo, const Scalar* hi) && { this->set_bounds(*res_, P_, lo, hi); return std::move(*this); }
   RaggedJitModel& with_prior(const Scalar* mu, const Scalar* W, int rows = 0) & { this->set_prior(*res_, P_, mu, W, rows); return *this; }
   RaggedJitModel&& with_prior(const Scalar* mu, const Scalar* W, int rows = 0) && { this->set_prior(*res_, P_, mu, W, rows); return std::move(*this); }
   RaggedJitModel(const JitResidual<Scalar>& res, const std::vector<int64_t>& counts, const Scalar* host, const Scalar* header)
@@ -549,6 +600,16 @@ template <typename C>
 inline bool has_prior(const C& cost) {
   if constexpr (takes_prior<C>::value) return cost.has_prior();
   else return false;
+}
+template <typename C, typename = void> struct takes_bounds : std::false_type {};
+template <typename C> struct takes_bounds<C, std::void_t<decltype(std::declval<const C&>().has_bounds())>> : std::true_type {};
+template <typename C>
+inline bool has_bounds(const C& cost) {
+  if constexpr (takes_bounds<C>::value) return cost.has_bounds();
+  else return false;
+}
+inline void refuse_bounds(const char* what) {
+  throw std::invalid_argument(std::string("tinyopt_amd: box bounds (with_bounds) stand on a Euclidean residual model in the one-launch form only: ") + what);
 }
 inline void refuse_prior(const char* what) {
   throw std::invalid_argument(std::string("tinyopt_amd: a Gaussian prior (with_prior) stands beside a Euclidean residual model in the one-launch form only: ") + what);
@@ -608,6 +669,10 @@ BatchOutput Optimize(std::vector<Scalar>& x, const Cost& cost, const Options& op
       throw std::invalid_argument("tinyopt_amd::Optimize: a numerically differentiated model runs as one launch per solve: stop callbacks, "
                                   "max_duration_ms and the log line are not supported (it has no stepping form)");
   }
+  if (detail::has_bounds(cost)) {
+    if (options.has_host_controls()) detail::refuse_bounds("no stepping form, so no host controls (stop callbacks, max_duration_ms, the log line)");
+    if (gd) detail::refuse_bounds("no GradientDescent");
+  }
   if (detail::has_prior(cost)) {
     if (options.has_host_controls()) detail::refuse_prior("no stepping form, so no host controls (stop callbacks, max_duration_ms, the log line)");
     if (gd) detail::refuse_prior("no GradientDescent");
@@ -653,6 +718,11 @@ BatchOutput Optimize(std::vector<Scalar>& x, const Cost& cost, const Options& op
       const toa_gd_options gpod = options.gd_pod();
       check(toa_jit_gd_run_ragged(ctx.get(), cost.ragged_handle(), cost.offsets_dev(), cost.header(), cost.max_items(), cost.total_items(), P,
                                   cost.data(), dx.data(), &pod, &gpod, &r, nullptr, flags));
+    } else if (cost.has_bounds()) {
+      const toa_bounds bd = cost.bounds_pod();
+      const toa_prior pr = cost.has_prior() ? cost.prior_pod() : toa_prior{};
+      check(toa_jit_lm_run_ragged_bounds(ctx.get(), cost.ragged_handle(), cost.offsets_dev(), cost.header(), cost.max_items(), cost.total_items(), P,
+                                         cost.data(), dx.data(), &bd, cost.has_prior() ? &pr : nullptr, &pod, &r, nullptr, flags));
     } else if (cost.has_prior()) {
       const toa_prior pr = cost.prior_pod();
       check(toa_jit_lm_run_ragged_prior(ctx.get(), cost.ragged_handle(), cost.offsets_dev(), cost.header(), cost.max_items(), cost.total_items(), P,
@@ -665,6 +735,11 @@ BatchOutput Optimize(std::vector<Scalar>& x, const Cost& cost, const Options& op
     if (gd) {   // gd::Optimizer on a scalar cost model (the library refuses any other model: optimize.h:59-75)
       const toa_gd_options gpod = options.gd_pod();
       check(toa_jit_gd_run(ctx.get(), cost.jit_handle(), cost.items(), P, cost.data(), dx.data(), &pod, &gpod, &r, nullptr));
+    } else if (cost.has_bounds()) {
+      const toa_bounds bd = cost.bounds_pod();
+      const toa_prior pr = cost.has_prior() ? cost.prior_pod() : toa_prior{};
+      check(toa_jit_lm_run_bounds(ctx.get(), cost.jit_handle(), cost.items(), P, cost.data(), dx.data(), &bd, cost.has_prior() ? &pr : nullptr, &pod, &r,
+                                  nullptr));
     } else if (cost.has_prior()) {
       const toa_prior pr = cost.prior_pod();
       check(toa_jit_lm_run_prior(ctx.get(), cost.jit_handle(), cost.items(), P, cost.data(), dx.data(), &pr, &pod, &r, nullptr));
@@ -700,6 +775,7 @@ GradientCheck CheckGradient(const JitModel<Scalar>& model, const std::vector<Sca
   const int64_t P = model.P();
   if (int64_t(x.size()) != P * model.xdim())
     throw std::invalid_argument("tinyopt_amd::diff::CheckGradient: x must hold P * (parameters per problem) scalars");
+  if (model.has_bounds()) detail::refuse_bounds("no CheckGradient (it checks the model's own rows)");
   if (model.has_prior()) detail::refuse_prior("no CheckGradient (it checks the model's own rows)");
   const Context& ctx = model.ctx();
   DeviceBuffer<Scalar> dx(ctx, x.size());
@@ -734,6 +810,7 @@ std::pair<std::vector<Scalar>, std::vector<Scalar>> Eval(const JitModel<Scalar>&
   const int64_t P = model.P();
   if (int64_t(x.size()) != P * model.xdim())
     throw std::invalid_argument("tinyopt_amd::diff::Eval: x must hold P * (parameters per problem) scalars");
+  if (model.has_bounds()) detail::refuse_bounds("no Eval / CalculateJac (they return the model's own rows)");
   if (model.has_prior()) detail::refuse_prior("no Eval / CalculateJac (they return the model's own rows)");
   const Context& ctx = model.ctx();
   const size_t rows = size_t(P) * size_t(model.m());
@@ -755,6 +832,7 @@ std::vector<Scalar> CalculateJac(const JitModel<Scalar>& model, const std::vecto
   const int64_t P = model.P();
   if (int64_t(x.size()) != P * model.xdim())
     throw std::invalid_argument("tinyopt_amd::diff::CalculateJac: x must hold P * (parameters per problem) scalars");
+  if (model.has_bounds()) detail::refuse_bounds("no Eval / CalculateJac (they return the model's own rows)");
   if (model.has_prior()) detail::refuse_prior("no Eval / CalculateJac (they return the model's own rows)");
   const Context& ctx = model.ctx();
   const size_t elems = size_t(P) * size_t(model.m()) * size_t(model.n());
@@ -774,6 +852,7 @@ std::pair<std::vector<Scalar>, std::vector<Scalar>> Eval(const RaggedJitModel<Sc
   const int64_t P = model.P();
   if (int64_t(x.size()) != P * model.xdim())
     throw std::invalid_argument("tinyopt_amd::diff::Eval: x must hold P * (parameters per problem) scalars");
+  if (model.has_bounds()) detail::refuse_bounds("no Eval / CalculateJac (they return the model's own rows)");
   if (model.has_prior()) detail::refuse_prior("no Eval / CalculateJac (they return the model's own rows)");
   const Context& ctx = model.ctx();
   const size_t rows = size_t(model.rows());
@@ -811,6 +890,7 @@ class Optimizer {
         state_(cost.ctx(), toa_lm_state_bytes(dtype_of<Scalar>(), n_, P_)) {
     if (int64_t(x.size()) != P_ * cost.xdim())
       throw std::invalid_argument("tinyopt_amd::Optimizer: x must hold P * (parameters per problem) scalars");
+    if (detail::has_bounds(cost)) detail::refuse_bounds("no stepping form (Optimizer)");
     if (detail::has_prior(cost)) detail::refuse_prior("no stepping form (Optimizer)");
     dx_.upload(x.data());
     stop_.zero(); iters_.zero(); fc_.zero();

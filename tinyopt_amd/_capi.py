@@ -87,6 +87,10 @@ class ToaPrior(C.Structure):   # include/tinyopt_amd.h toa_prior (rows = 0: the 
     _fields_ = [("mu_dev", C.c_void_p), ("W_dev", C.c_void_p), ("rows", C.c_int32), ("reserved", C.c_int32 * 5)]
 
 
+class ToaBounds(C.Structure):   # include/tinyopt_amd.h toa_bounds (-inf / +inf: no bound; lo == hi: fixed)
+    _fields_ = [("lo_dev", C.c_void_p), ("hi_dev", C.c_void_p), ("reserved", C.c_int32 * 4)]
+
+
 _P = C.c_void_p
 PROTOTYPES = {
     "toa_options_default": (None, [C.POINTER(ToaOptions)]),
@@ -157,6 +161,14 @@ PROTOTYPES = {
                                               C.POINTER(ToaResults), _P, C.c_uint32]),
     "toa_jit_accumulate_ragged_prior": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int64, C.c_int64, _P, _P, C.POINTER(ToaPrior), C.c_int, _P, _P, _P, _P]),
     "toa_jit_model_stats_prior": (C.c_int, [_P, _P, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "toa_jit_lm_run_bounds": (C.c_int, [_P, _P, C.c_int, C.c_int64, _P, _P, C.POINTER(ToaBounds), C.POINTER(ToaPrior), C.POINTER(ToaOptions),
+                                        C.POINTER(ToaResults), _P]),
+    "toa_jit_lm_run_ragged_bounds": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int64, C.c_int64, _P, _P, C.POINTER(ToaBounds), C.POINTER(ToaPrior),
+                                               C.POINTER(ToaOptions), C.POINTER(ToaResults), _P, C.c_uint32]),
+    "toa_jit_accumulate_bounds": (C.c_int, [_P, _P, C.c_int, C.c_int64, _P, _P, C.POINTER(ToaBounds), C.POINTER(ToaPrior), C.c_int, _P, _P, _P, _P]),
+    "toa_jit_accumulate_ragged_bounds": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int64, C.c_int64, _P, _P, C.POINTER(ToaBounds), C.POINTER(ToaPrior),
+                                                   C.c_int, _P, _P, _P, _P]),
+    "toa_jit_model_stats_bounds": (C.c_int, [_P, _P, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "toa_gd_options_default": (None, [C.POINTER(ToaGdOptions)]),
     "toa_jit_gd_run": (C.c_int, [_P, _P, C.c_int, C.c_int64, _P, _P, C.POINTER(ToaOptions), C.POINTER(ToaGdOptions), C.POINTER(ToaResults), _P]),
     "toa_jit_lm_run_split": (C.c_int, [_P, _P, C.c_int, C.c_int64, _P, _P, C.POINTER(ToaOptions), C.POINTER(ToaResults), _P, C.c_int]),

@@ -336,6 +336,69 @@ class _PriorMixin:
         return pod
 
 
+class _BoundsMixin:
+    """Bound run-time models that keep parameters inside a box: ``model.with_bounds(lo, hi)`` — per problem ``lo[p, j] <= x[p, j] <=
+    hi[p, j]``, ``[P, n]`` tensors of the model's dtype and device; ``None`` for a side means no bound there (-inf / +inf), and
+    ``lo[p, j] == hi[p, j]`` holds parameter j of problem p constant.  x0 is clipped into the box before the first Build; after every
+    Build the parameters that sit on a bound with the gradient pointing outward (and the fixed ones) are taken out of the system
+    (g_j = 0, row and column j of H zero, H_jj = 1), so their step is 0 and ``min_grad_norm2`` tests the projected gradient; every
+    step is clipped, and a roll-back undoes the clipped step.  Every x the solve visits and returns is inside the box exactly.
+    ``Output.final_hessian`` is the projected matrix of the last Build, so ``Output.Covariance()`` is the inverse of the free block
+    for the free parameters and 1 on the diagonal of the active ones.  Clip-and-reject, not a trust-region reflection: with a small
+    ``max_consec_failures`` a solve can stop with kMaxConsecNoDecr short of the constrained optimum — raise it (30) for hard boxes.
+    Composes with ``with_loss`` and ``with_prior`` in any order.  Euclidean residual models only; no ``splits`` (and never the
+    automatic row-split), no host controls, no ``Optimizer``, no ``Eval`` / ``CalculateJac`` / ``CheckGradient``."""
+    bounds = None   # (lo, hi)
+
+    def with_bounds(self, lo: Optional[torch.Tensor], hi: Optional[torch.Tensor]):
+        import copy
+        res = self.res
+        if getattr(res, "large_n", False):
+            _refuse_large_n("no box bounds (with_bounds)")
+        if res.kind in JitResidual.COST_KINDS:
+            _refuse_bounds('a scalar cost model (kind="cost" / "cost_grad", GradientDescent) has no Gauss-Newton system to project')
+        if res.manifold != "euclid":
+            _refuse_bounds(f'manifold={res.manifold!r}: a box on the tangent is not a box on the parameter (Euclidean parameters only)')
+        P, n = self.P, self.n
+        dev = self._prior_device()
+        sides = []
+        for name, t, fill in (("lo", lo, float("-inf")), ("hi", hi, float("inf"))):
+            if t is None:
+                t = torch.full((P, n), fill, dtype=self.dtype, device=dev)
+            if not isinstance(t, torch.Tensor):
+                raise ValueError(f"with_bounds: {name} must be a tensor or None")
+            if tuple(t.shape) != (P, n):
+                raise ValueError(f"with_bounds: {name} must be [P, n] = [{P}, {n}], not {list(t.shape)}")
+            if t.dtype != self.dtype:
+                raise ValueError(f"with_bounds: {name} must have the model's dtype {self.dtype}, not {t.dtype}")
+            if t.device != dev:
+                raise ValueError(f"with_bounds: {name} must be on the model's device {dev}, not {t.device}")
+            sides.append(t.contiguous())
+        # one device reduction, here and never per solve (a NaN fails the comparison)
+        if P * n > 0 and not bool((sides[0] <= sides[1]).all()):
+            raise ValueError("with_bounds: lo <= hi must hold for every parameter of every problem, without NaN")
+        m = copy.copy(self)          # shares the device data
+        m.bounds = (sides[0], sides[1])
+        return m
+
+    def _bounds_pod(self):
+        from ._capi import ToaBounds
+        pod = ToaBounds()
+        pod.lo_dev, pod.hi_dev = self.bounds[0].data_ptr(), self.bounds[1].data_ptr()
+        return pod
+
+    def _prior_ref(self):
+        """(pod kept alive by the caller, its byref or NULL) for the *_bounds entries"""
+        if self.prior is None:
+            return None, None
+        pr = self._prior_pod()
+        return pr, C.byref(pr)
+
+
+def _refuse_bounds(what: str):
+    raise ValueError(f"box bounds (with_bounds) stand on a Euclidean residual model in the one-launch form only: {what}")
+
+
 def _refuse_large_n(what: str):
     raise ValueError(f"a model compiled with large_n=True runs on the launch-per-phase pipeline through Optimize (LM / GN), accumulate, Eval "
                      f"and CalculateJac only: {what}")
@@ -576,7 +639,7 @@ class JitResidual:
     run through both routes), ``item_scalars`` up to 2048, ``kind="residual"`` (chunked Jets) or ``"accumulate"``, Euclidean
     parameters, ``diff="ad"``.  ``Optimize`` (LM / GN), ``accumulate``, ``Eval`` and ``CalculateJac`` take such a model; everything
     else is refused with a sentence: cost kinds and GradientDescent, manifolds, numerical differentiation, ``CheckGradient``,
-    ``with_loss``, ``with_prior``, ``bind_ragged``, ``splits``, the stepping ``Optimizer``, host controls, stream capture of the
+    ``with_loss``, ``with_prior``, ``with_bounds``, ``bind_ragged``, ``splits``, the stepping ``Optimizer``, host controls, stream capture of the
     solve.  Without ``large_n`` a model of 64 parameters is refused as before.  ``stats()`` then describes the rows kernel."""
 
     MANIFOLDS = {"euclid": 0, "se3": 1, "user": 2}
@@ -666,6 +729,13 @@ class JitResidual:
         check(self.ctx.lib.toa_jit_model_stats_prior(self.ctx.h, self._h, int(bool(ragged)), *[C.byref(t) for t in v]))
         return dict(wg_per_cu=v[0].value, num_regs=v[1].value, scratch_bytes=v[2].value)
 
+    def stats_bounds(self, ragged: bool = False, with_prior: bool = False) -> dict:
+        """``stats_ragged`` of the fused kernel with box bounds (``with_bounds``) in the form named by ``ragged`` / ``with_prior`` (its
+        plain L2 build, compiled by this call if it was not yet)."""
+        v = [C.c_int(0) for _ in range(3)]
+        check(self.ctx.lib.toa_jit_model_stats_bounds(self.ctx.h, self._h, int(bool(ragged)), int(bool(with_prior)), *[C.byref(t) for t in v]))
+        return dict(wg_per_cu=v[0].value, num_regs=v[1].value, scratch_bytes=v[2].value)
+
     def stats_ragged(self) -> dict:
         """``stats`` of the ragged fused kernel (its plain L2 build, compiled by this call if it was not yet)."""
         v = [C.c_int(0) for _ in range(3)]
@@ -684,7 +754,7 @@ class JitResidual:
             pass
 
 
-class JitModel(_LossMixin, _PriorMixin):
+class JitModel(_LossMixin, _PriorMixin, _BoundsMixin):
     """A JitResidual bound to its problem data ([P][header | items x item_scalars], the layout of the built-in Jet families)."""
     model_id = None
 
@@ -740,7 +810,7 @@ def ragged_offsets(counts=None, offsets=None, total_items: Optional[int] = None)
     return off
 
 
-class RaggedJitModel(_LossMixin, _PriorMixin):
+class RaggedJitModel(_LossMixin, _PriorMixin, _BoundsMixin):
     """A JitResidual bound to a RAGGED batch: data [total_items, item_scalars] (the items of all problems, one after another), a
     separate header [P, header_scalars] and int64 offsets [P + 1].  Taken by ``Optimize`` (LM, GN; GradientDescent for cost kinds),
     ``accumulate``, ``Eval`` and ``CalculateJac``; every problem computes bit for bit what it would alone in a uniform batch of
@@ -1077,6 +1147,19 @@ def Optimize(x: torch.Tensor, cost, options: Optional[Options] = None, *, histor
                                        cost.obs_cam.data_ptr(), cost.obs_pt.data_ptr(), cost.obs_uv.data_ptr(), x.data_ptr(),
                                        C.byref(pod), C.byref(res), out.counters.data_ptr(), float(options.max_duration_ms or 0.0)))
         return out
+    if isinstance(cost, JitModel) and cost.bounds is not None:
+        if splits is not None:
+            _refuse_bounds("no row-split form (splits)")
+        if options.has_host_controls():
+            _refuse_bounds("no stepping form, so no host controls (stop callbacks, max_duration_ms, the log line)")
+        if options.solver_type == Options.GradientDescent:
+            _refuse_bounds("no GradientDescent")
+        pod, out, res = _run_prologue(x, cost, n, options, history, ctx, out, zero_counters)
+        bd = cost._bounds_pod()
+        pr, pr_ref = cost._prior_ref()
+        check(ctx.lib.toa_jit_lm_run_bounds(ctx.h, cost.res._h, cost.items, P, cost.packed.data_ptr(), x.data_ptr(), C.byref(bd), pr_ref, C.byref(pod),
+                                            C.byref(res), out.counters.data_ptr()))
+        return out
     if isinstance(cost, JitModel) and cost.prior is not None:
         if splits is not None:
             _refuse_prior("no row-split form (splits)")
@@ -1157,6 +1240,8 @@ def _optimize_ragged(x: torch.Tensor, cost: "RaggedJitModel", options: Options, 
         _refuse_ragged("no row-split form (splits)")
     if options.has_host_controls():
         _refuse_ragged("no stepping form, so no host controls (stop callbacks, max_duration_ms, the log line)")
+    if cost.bounds is not None and options.solver_type == Options.GradientDescent:
+        _refuse_bounds("no GradientDescent")
     if cost.prior is not None and options.solver_type == Options.GradientDescent:
         _refuse_prior("no GradientDescent")
     P = x.shape[0]
@@ -1170,6 +1255,11 @@ def _optimize_ragged(x: torch.Tensor, cost: "RaggedJitModel", options: Options, 
         gd.lr = float(options.gd.lr)
         check(ctx.lib.toa_jit_gd_run_ragged(ctx.h, cost.res._h, *cost._ragged_args(), P, cost.data.data_ptr(), x.data_ptr(), C.byref(pod),
                                             C.byref(gd), C.byref(res), out.counters.data_ptr(), flags))
+    elif cost.bounds is not None:
+        bd = cost._bounds_pod()
+        pr, pr_ref = cost._prior_ref()
+        check(ctx.lib.toa_jit_lm_run_ragged_bounds(ctx.h, cost.res._h, *cost._ragged_args(), P, cost.data.data_ptr(), x.data_ptr(), C.byref(bd), pr_ref,
+                                                   C.byref(pod), C.byref(res), out.counters.data_ptr(), flags))
     elif cost.prior is not None:
         pr = cost._prior_pod()
         check(ctx.lib.toa_jit_lm_run_ragged_prior(ctx.h, cost.res._h, *cost._ragged_args(), P, cost.data.data_ptr(), x.data_ptr(), C.byref(pr),
@@ -1192,6 +1282,8 @@ class Optimizer:
         _check_call(x, cost)
         if isinstance(cost, RaggedJitModel):
             _refuse_ragged("no stepping form (Optimizer)")
+        if getattr(cost, "bounds", None) is not None:
+            _refuse_bounds("no stepping form (Optimizer)")
         if getattr(cost, "prior", None) is not None:
             _refuse_prior("no stepping form (Optimizer)")
         if isinstance(cost, JitModel) and cost.res.diff != "ad":
@@ -1396,6 +1488,17 @@ def accumulate(cost, x: torch.Tensor, want_grad: bool = True, ctx: Optional[Cont
     c = torch.zeros(P, dtype=torch.float64, device=dev)
     nres = torch.zeros(P, dtype=torch.int32, device=dev)
     _apply_loss(ctx, cost)
+    if getattr(cost, "bounds", None) is not None:   # (x as given; the active set applied to g and H; with the prior if there is one)
+        bd = cost._bounds_pod()
+        pr, pr_ref = cost._prior_ref()
+        gp, Hp = (g.data_ptr(), H.data_ptr()) if want_grad else (None, None)
+        if isinstance(cost, RaggedJitModel):
+            check(ctx.lib.toa_jit_accumulate_ragged_bounds(ctx.h, cost.res._h, *cost._ragged_args(), P, cost.data.data_ptr(), x.data_ptr(), C.byref(bd),
+                                                           pr_ref, int(want_grad), gp, Hp, c.data_ptr(), nres.data_ptr()))
+        else:
+            check(ctx.lib.toa_jit_accumulate_bounds(ctx.h, cost.res._h, cost.items, P, cost.packed.data_ptr(), x.data_ptr(), C.byref(bd), pr_ref,
+                                                    int(want_grad), gp, Hp, c.data_ptr(), nres.data_ptr()))
+        return g, H, c, nres
     if getattr(cost, "prior", None) is not None:   # (never a cost kind: with_prior refuses those)
         pr = cost._prior_pod()
         gp, Hp = (g.data_ptr(), H.data_ptr()) if want_grad else (None, None)
@@ -1446,6 +1549,8 @@ def CheckGradient(model: "JitModel", x: torch.Tensor, eps: Optional[float] = Non
     x [P, n]: the model's own derivatives against finite differences of its residuals (or cost terms) with step eps / 10.
     Residual kinds compare g = J^T r and, with ``check_H``, H = J^T J; cost kinds compare g.  ``eps`` None: the reference's default
     (1e-2 in float32, 1e-5 in float64).  The first check of a model with a (method, eps) compiles its numeric twin (then cached)."""
+    if getattr(model, "bounds", None) is not None:
+        _refuse_bounds("no CheckGradient (it checks the model's own rows: check the model without the bounds)")
     if getattr(model, "prior", None) is not None:
         _refuse_prior("no CheckGradient (it checks the model's own rows: check the model without the prior)")
     if isinstance(model, RaggedJitModel):
@@ -1487,6 +1592,8 @@ def Eval(model: "JitModel", x: torch.Tensor, jac: bool = True, ctx: Optional[Con
     Not for scalar costs (``accumulate`` already returns their value and gradient) and not with a loss set.  ``res_out`` /
     ``J_out``: write into the caller's tensors (views are fine as long as they are contiguous).  The first call of a model
     compiles its Eval kernels (then cached)."""
+    if getattr(model, "bounds", None) is not None:
+        _refuse_bounds("no Eval (it returns the model's own rows: evaluate the model without the bounds)")
     if getattr(model, "prior", None) is not None:
         _refuse_prior("no Eval (it returns the model's own rows: evaluate the model without the prior)")
     if isinstance(model, RaggedJitModel):   # outputs concatenated like the items: res [rows], J [rows, n]
@@ -1513,6 +1620,8 @@ def Eval(model: "JitModel", x: torch.Tensor, jac: bool = True, ctx: Optional[Con
 
 def CalculateJac(model: "JitModel", x: torch.Tensor, ctx: Optional[Context] = None, *, J_out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """``diff::CalculateJac(x, f)`` (diff/auto_diff.h:120-138): the Jacobian rows J [P, m, n] alone (see ``Eval``)."""
+    if getattr(model, "bounds", None) is not None:
+        _refuse_bounds("no CalculateJac (it returns the model's own rows: evaluate the model without the bounds)")
     if getattr(model, "prior", None) is not None:
         _refuse_prior("no CalculateJac (it returns the model's own rows: evaluate the model without the prior)")
     if isinstance(model, RaggedJitModel):

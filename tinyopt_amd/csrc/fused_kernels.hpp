@@ -3,6 +3,7 @@
 #pragma once
 #include "models_jet.hpp"
 #include "prior.hpp"
+#include "bounds.hpp"
 
 namespace toa {
 
@@ -75,6 +76,14 @@ struct PriorFusedParams {
   FusedParams f;
   RaggedArgs ragged;
   PriorArgs prior;
+};
+// ... and of a launch with box bounds (bounds.hpp), in any of the forms above: the prior block, then the bounds (a launch without a
+// prior or a ragged batch leaves those zero).  Only a code object built with TOA_BOUNDS reads that far.
+struct BoundsFusedParams {
+  FusedParams f;
+  RaggedArgs ragged;
+  PriorArgs prior;
+  BoundsArgs bounds;
 };
 
 template <typename M, typename = void>
@@ -156,6 +165,9 @@ __global__ void __launch_bounds__(64 * ModelWaves<Model>::value) TOA_FUSED_ATTR 
 #ifdef TOA_PRIOR
   model.set_prior(reinterpret_cast<const PriorFusedParams*>(prm_g)->prior, L.M, L.LD);
 #endif
+#ifdef TOA_BOUNDS
+  model.set_bounds(reinterpret_cast<const BoundsFusedParams*>(prm_g)->bounds, L.M, L.LD);
+#endif
   if constexpr (ModelStageBytes<Model>::value > 0) model.stage = reinterpret_cast<unsigned char*>(smem) + size_t(wave) * prm_g->lds_per_wave + prm_g->stage_off;
   T* X = static_cast<T*>(prm_g->x);
   const int xd = Model::kXdim ? Model::kXdim : n;  // stored parameters per problem (SE3: 12 for n = 6)
@@ -228,6 +240,9 @@ __global__ void __launch_bounds__(64 * ModelWaves<Model>::value) TOA_FUSED_ATTR 
     model.bind(p);
     wave_sync();
     L.xs[lane] = (lane < xd && !ghost) ? X[size_t(p) * xd + lane] : T(0);
+#ifdef TOA_BOUNDS
+    if (!ghost) model.project_start(L, lane);   // x0 into the box, before the first Build
+#endif
     wave_sync();
     const unsigned long long tl0 = prm_g->timeline ? wall_clock64() : 0ull;
     lm_solve_problem<T>(model, L, n, lane, ghost ? -1ll : (long long)p);
@@ -261,7 +276,7 @@ __global__ void __launch_bounds__(64 * ModelWaves<Model>::value) TOA_FUSED_ATTR 
 template <typename Model>
 __global__ void __launch_bounds__(256) accumulate_kernel(const void* data_, const void* x_, long long P, int n, int m,
                                                          int want_grad, void* g_, void* H_, double* cost, int* nres,
-                                                         int lds_per_wave, int loss, double loss_th2 TOA_RAGGED_KARG TOA_PRIOR_KARG) {
+                                                         int lds_per_wave, int loss, double loss_th2 TOA_RAGGED_KARG TOA_PRIOR_KARG TOA_BOUNDS_KARG) {
   using T = typename Model::Scalar;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -275,6 +290,9 @@ __global__ void __launch_bounds__(256) accumulate_kernel(const void* data_, cons
   WaveLds<T> L = WaveLds<T>::carve(model_bind_stage(model, smem + size_t(wave) * lds_per_wave, n), n);
 #ifdef TOA_PRIOR
   model.set_prior(pri, L.M, L.LD);
+#endif
+#ifdef TOA_BOUNDS
+  model.set_bounds(bnd, L.M, L.LD);   // (the seam takes x as given: no start projection)
 #endif
   const int xd = Model::kXdim ? Model::kXdim : n;
   for (long long p = (long long)blockIdx.x * 4 + wave; p < P; p += (long long)gridDim.x * 4) {

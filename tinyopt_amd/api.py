@@ -7,8 +7,12 @@ Names and meanings follow the reference:
 """
 from __future__ import annotations
 
+import contextlib
+import copy
 import ctypes as C
 import enum
+import functools
+import time
 
 import numpy as np
 from dataclasses import dataclass, field
@@ -18,7 +22,7 @@ import torch
 
 from . import _capi
 from ._capi import (F32, F64, MODEL_DENSE_ROW_AD, MODEL_DENSE_ROW_NATURAL, MODEL_TESTFN, MODEL_MAHA_PRIOR, MODEL_SE3_PRIOR, MODEL_CIRCLE_FIT, MODEL_DENSE_ROW, MODEL_DENSE_ROW_AD6, MODEL_GAUSSIAN_PRIOR, MODEL_SE3_REPROJ,
-                    MODEL_SQRT2, ToaOptions, ToaResults, check)
+                    MODEL_SQRT2, ToaBounds, ToaGdOptions, ToaJitSpec, ToaOptions, ToaPrior, ToaResults, check)
 
 
 class StopReason(enum.IntEnum):  # include/tinyopt/stop_reasons.h:14-43
@@ -152,6 +156,9 @@ class Options:
         return p
 
 
+_GRADIENT_DESCENT = Options.GradientDescent
+
+
 def _dtype_code(dt: torch.dtype) -> int:
     if dt == torch.float32:
         return F32
@@ -211,8 +218,6 @@ class Context:
 
     def tuning(self, **kw):
         """``with ctx.tuning(coop_off=1): ...`` — the fields set for the block, the previous state restored after it."""
-        import contextlib
-
         @contextlib.contextmanager
         def cm():
             old = self.get_tuning()
@@ -264,26 +269,39 @@ def dense_row_layout(dtype: torch.dtype, n: int, m: int):
             "pos_b": (rs.value - 1) if thin.value else (rsm - 1)}
 
 
-class _LossMixin:
+class _Model:
+    """What every device model is to the entry points.  ``route``: which family of library entries takes it ("builtin": the compiled-in
+    ``model_id`` families, "ba", "ba_lists", "jit": a bound run-time model, see ``_JitBatch``)."""
+    route = "builtin"
+    model_id = None
+    loss, th = None, 0.0
+    prior = None        # (mu, W, rows): rows = 0 the diagonal form
+    bounds = None       # (lo, hi)
+    ragged = large_n = header_l2 = False
+    xdim = functools.cached_property(lambda self: self.n)   # scalars of x per problem, where a model does not say
+
+    def _head(self, ctx: "Context", x: torch.Tensor) -> tuple:
+        """What every library entry over a batch starts with: the handle, the batch, x."""
+        return (ctx.h, self.model_id, _dtype_code(x.dtype), self.n, self.m, x.shape[0], self.packed.data_ptr(), x.data_ptr())
+
+
+class _LossMixin(_Model):
     """Models whose residual items can be wrapped in one of the reference's M-estimators (losses/robust_norms.h:32-316):
     ``model.with_loss("huber", th)`` is the device counterpart of calling ``losses::Huber(n2, th*th, true)`` on each
     residual's squared norm inside the cost functor (docs/API.md:396-411).  cost += l, the item's J^T J and J^T r are
     scaled by s = dl/dn2, and Output.final_inlier_ratio reports the residuals with n2 <= th^2 (cost.h:84-95)."""
-    loss: Optional[str] = None
-    th: float = 0.0
 
     def with_loss(self, loss: Optional[str], th: float = 0.0):
-        import copy
         if loss is not None and loss not in LOSS_KINDS:
             raise ValueError(f"unknown loss {loss!r}; one of {sorted(LOSS_KINDS)}")
-        if loss not in (None, "l2") and getattr(getattr(self, "res", None), "large_n", False):
+        if loss not in (None, "l2") and self.large_n:
             _refuse_large_n("no M-estimator (with_loss): the pipeline's loss is per row, an item's is on its squared norm")
         m = copy.copy(self)          # shares the device data
         m.loss, m.th = (loss if loss not in (None, "l2") else None), float(th)
         return m
 
 
-class _PriorMixin:
+class _PriorMixin(_Model):
     """Bound run-time models that take a Gaussian prior beside their items: ``model.with_prior(mu, W)`` — per problem
     ``r = W (x - mu)`` appended to the items' residuals after every pass (cost += |r|^2, g += W^T r, H += W^T W, k more
     residuals), what a hand-written Accumulate callback of the reference adds at its end.  ``mu``: [P, n].  ``W``: [P, n] is the
@@ -292,12 +310,9 @@ class _PriorMixin:
     ``Output.Covariance()`` of a prior'd run is the posterior covariance.  Composes with ``with_loss``.  Euclidean residual models
     only; no ``splits`` (and never the automatic row-split), no host controls, no ``Optimizer``, no ``Eval`` / ``CalculateJac`` /
     ``CheckGradient`` (those are about the model's own rows)."""
-    prior = None   # (mu, W, rows): rows = 0 the diagonal form
-
     def with_prior(self, mu: torch.Tensor, W: torch.Tensor):
-        import copy
         res = self.res
-        if getattr(res, "large_n", False):
+        if self.large_n:
             _refuse_large_n("no Gaussian prior (with_prior)")
         if res.kind in JitResidual.COST_KINDS:
             _refuse_prior('a scalar cost model (kind="cost" / "cost_grad", GradientDescent) has no residuals to add a prior to')
@@ -330,13 +345,12 @@ class _PriorMixin:
         return m
 
     def _prior_pod(self):
-        from ._capi import ToaPrior
         pod = ToaPrior()
         pod.mu_dev, pod.W_dev, pod.rows = self.prior[0].data_ptr(), self.prior[1].data_ptr(), self.prior[2]
         return pod
 
 
-class _BoundsMixin:
+class _BoundsMixin(_Model):
     """Bound run-time models that keep parameters inside a box: ``model.with_bounds(lo, hi)`` — per problem ``lo[p, j] <= x[p, j] <=
     hi[p, j]``, ``[P, n]`` tensors of the model's dtype and device; ``None`` for a side means no bound there (-inf / +inf), and
     ``lo[p, j] == hi[p, j]`` holds parameter j of problem p constant.  x0 is clipped into the box before the first Build; after every
@@ -348,12 +362,9 @@ class _BoundsMixin:
     ``max_consec_failures`` a solve can stop with kMaxConsecNoDecr short of the constrained optimum — raise it (30) for hard boxes.
     Composes with ``with_loss`` and ``with_prior`` in any order.  Euclidean residual models only; no ``splits`` (and never the
     automatic row-split), no host controls, no ``Optimizer``, no ``Eval`` / ``CalculateJac`` / ``CheckGradient``."""
-    bounds = None   # (lo, hi)
-
     def with_bounds(self, lo: Optional[torch.Tensor], hi: Optional[torch.Tensor]):
-        import copy
         res = self.res
-        if getattr(res, "large_n", False):
+        if self.large_n:
             _refuse_large_n("no box bounds (with_bounds)")
         if res.kind in JitResidual.COST_KINDS:
             _refuse_bounds('a scalar cost model (kind="cost" / "cost_grad", GradientDescent) has no Gauss-Newton system to project')
@@ -382,17 +393,39 @@ class _BoundsMixin:
         return m
 
     def _bounds_pod(self):
-        from ._capi import ToaBounds
         pod = ToaBounds()
         pod.lo_dev, pod.hi_dev = self.bounds[0].data_ptr(), self.bounds[1].data_ptr()
         return pod
 
-    def _prior_ref(self):
-        """(pod kept alive by the caller, its byref or NULL) for the *_bounds entries"""
-        if self.prior is None:
-            return None, None
-        pr = self._prior_pod()
-        return pr, C.byref(pr)
+
+class _JitBatch(_LossMixin, _PriorMixin, _BoundsMixin):
+    """A bound run-time model, uniform (``JitModel``) or ragged (``RaggedJitModel``), says here once what it hands the library — as
+    jit.hip's JitBatch does on the other side: ``_head`` (the handle, the batch, x), ``_extras`` (what follows x) and, with ``ragged``,
+    the key that picks the member of an entry family in ``_JIT_ENTRIES``.  A new per-model extra is one more branch of ``_extras`` and
+    one more column of that table."""
+    route, _plain = "jit", (False, None)
+    large_n = functools.cached_property(lambda self: getattr(self.res, "large_n", False))   # (tests/test_cpu_prior.py binds a residual without one)
+
+    def _extras(self):
+        """(the key (ragged, extra) of _JIT_ENTRIES, the extra's arguments): the bounds pod and the prior's or NULL, or the prior pod, or
+        nothing.  A byref holds its pod, so the tuple keeps them alive for the call."""
+        if self.bounds is not None:
+            return (self.ragged, "bounds"), (C.byref(self._bounds_pod()), C.byref(self._prior_pod()) if self.prior is not None else None)
+        if self.prior is not None:
+            return (self.ragged, "prior"), (C.byref(self._prior_pod()),)
+        return self._plain, ()
+
+
+_JIT_ENTRIES = {   # entry family -> (ragged, extra) -> the library entry
+    "lm_run": {(False, "prior"): "toa_jit_lm_run_prior", (False, "bounds"): "toa_jit_lm_run_bounds",
+               (True, None): "toa_jit_lm_run_ragged", (True, "prior"): "toa_jit_lm_run_ragged_prior", (True, "bounds"): "toa_jit_lm_run_ragged_bounds"},
+    "gd_run": {(False, None): "toa_jit_gd_run", (True, None): "toa_jit_gd_run_ragged"},
+    "accumulate": {(False, None): "toa_jit_accumulate", (False, "prior"): "toa_jit_accumulate_prior", (False, "bounds"): "toa_jit_accumulate_bounds",
+                   (True, None): "toa_jit_accumulate_ragged", (True, "prior"): "toa_jit_accumulate_ragged_prior",
+                   (True, "bounds"): "toa_jit_accumulate_ragged_bounds"},
+    "eval": {(False, None): "toa_jit_eval", (True, None): "toa_jit_eval_ragged"},
+}
+_STEP_ENTRIES = {False: ("toa_lm_begin", "toa_lm_step", "toa_lm_stop"), True: ("toa_jit_lm_begin", "toa_jit_lm_step", "toa_jit_lm_stop")}   # by route == "jit"
 
 
 def _refuse_bounds(what: str):
@@ -408,14 +441,88 @@ def _refuse_prior(what: str):
     raise ValueError(f"a Gaussian prior (with_prior) stands beside a Euclidean residual model in the one-launch form only: {what}")
 
 
+def _refuse_ragged(what: str):
+    raise ValueError(f"a ragged batch (bind_ragged) runs in the one-launch form only: {what}")
+
+
+def _refuse_plainly(what: str):
+    raise ValueError(what)
+
+
+# Every sentence a refusal of an entry point can end in, once: (what refuses, what is refused) -> the sentence.  What refuses is a name
+# of _who(cost); the first four speak through their _refuse_* prefix.  Each entry point consults the pairs of its own *_REFUSES tuple
+# in that tuple's order and raises the first that applies, before its first library call and before it allocates anything.  A new
+# refusal is one line here and one pair in the order of each entry point that makes it.
+_NO_SPLITS, _NO_HOST, _NO_GD, _NO_STEPPING = ("no row-split form (splits)", "no stepping form, so no host controls (stop callbacks, max_duration_ms, the log line)",
+                                              "no GradientDescent", "no stepping form (Optimizer)")
+_BA_ONE_LAUNCH = "BundleAdjustment runs as one launch per solve: no stop callbacks / splits"
+_BA_LISTS_ONE_LAUNCH = "BundleAdjustmentLists: no stop callbacks / splits (max_duration_ms is honoured)"
+_NUMERIC_ONE_LAUNCH = ("a numerically differentiated model (diff=...) runs as one launch per solve: no stop callbacks, max_duration_ms, "
+                       "log line or splits (it has no stepping and no row-split form)")
+_REFUSALS = {
+    **{(who, what): text for who in ("ragged", "bounds", "prior", "large_n")
+       for what, text in (("splits", _NO_SPLITS), ("host", _NO_HOST), ("gd", _NO_GD), ("Optimizer", _NO_STEPPING))},
+    ("large_n", "splits"): _NO_SPLITS + ": the pipeline already spreads a problem's rows over the device",   # (says more than the four share)
+    ("large_n", "capture"): "no stream capture of the solve (the host enqueues its passes)",
+    ("large_n", "CheckGradient"): "no CheckGradient (its numeric twin is a one-wavefront model of at most 63 parameters)",
+    ("ragged", "CheckGradient"): "no CheckGradient (check the model on a uniform batch: JitResidual.bind)",
+    **{(who, "CheckGradient"): f"no CheckGradient (it checks the model's own rows: check the model without the {who})" for who in ("bounds", "prior")},
+    **{(who, what): f"no {what} (it returns the model's own rows: evaluate the model without the {who})"
+       for who in ("bounds", "prior") for what in ("Eval", "CalculateJac")},
+    ("uniform", "keep_order"): "keep_order is the queue order of a ragged batch (JitResidual.bind_ragged)",
+    ("ba", "host"): _BA_ONE_LAUNCH, ("ba", "splits"): _BA_ONE_LAUNCH,
+    ("ba_lists", "callbacks"): _BA_LISTS_ONE_LAUNCH, ("ba_lists", "splits"): _BA_LISTS_ONE_LAUNCH,
+    ("numeric", "host"): _NUMERIC_ONE_LAUNCH, ("numeric", "splits"): _NUMERIC_ONE_LAUNCH,
+    ("numeric", "Optimizer"): "a numerically differentiated model (diff=...) has no stepping form",
+    ("gd_cost", "host"): "GradientDescent runs as one launch per solve: stop callbacks, max_duration_ms and the log line are not "
+                         "supported on this path (no stepping form for scalar costs)",
+    ("gd_cost", "splits"): "GradientDescent: no row-split form (splits)",
+    ("stepping", "out with host controls"): "stop callbacks / max_duration_ms run through the stepping form: splits / out are not taken",
+}
+_REFUSE_AS = {"ragged": _refuse_ragged, "bounds": _refuse_bounds, "prior": _refuse_prior, "large_n": _refuse_large_n}
+_OPTIMIZE_REFUSES = (("ragged", "splits"), ("ragged", "host"), ("uniform", "keep_order"), ("ba", "host"), ("ba", "splits"),
+                     ("ba_lists", "callbacks"), ("ba_lists", "splits"),
+                     ("bounds", "splits"), ("bounds", "host"), ("bounds", "gd"), ("prior", "splits"), ("prior", "host"), ("prior", "gd"),
+                     ("large_n", "splits"), ("large_n", "host"), ("large_n", "gd"), ("large_n", "capture"), ("numeric", "host"), ("numeric", "splits"),
+                     ("gd_cost", "host"), ("gd_cost", "splits"), ("stepping", "out with host controls"))
+_OPTIMIZER_REFUSES = tuple((who, "Optimizer") for who in ("ragged", "bounds", "prior", "numeric", "large_n"))
+_CHECK_GRADIENT_REFUSES = tuple((who, "CheckGradient") for who in ("bounds", "prior", "ragged", "large_n"))
+_ROWS_REFUSES = {what: (("bounds", what), ("prior", what)) for what in ("Eval", "CalculateJac")}
+
+
+def _who(cost, gd: bool = False) -> set:
+    """The names under which ``cost`` can refuse something (the first column of _REFUSALS); ``gd``: the options ask for GradientDescent."""
+    who = {cost.route, "ragged" if cost.ragged else "uniform"}
+    if cost.bounds is not None:
+        who.add("bounds")
+    if cost.prior is not None:
+        who.add("prior")
+    if cost.large_n:
+        who.add("large_n")
+    if cost.route == "jit" and cost.res.diff != "ad":
+        who.add("numeric")
+    if gd and cost.route == "jit" and cost.res.kind in JitResidual.COST_KINDS:
+        who.add("gd_cost")
+    if cost.route != "ba_lists":   # (it honours max_duration_ms itself; every other family goes to the stepping form for host controls)
+        who.add("stepping")
+    return who
+
+
+def _refuse(order, who, asked) -> None:
+    """Raise the first refusal of ``order`` whose first half is in ``who`` and whose second is in ``asked``."""
+    for key in order:
+        if key[0] in who and key[1] in asked:
+            _REFUSE_AS.get(key[0], _refuse_plainly)(_REFUSALS[key])
+
+
 def _apply_loss(ctx: "Context", cost) -> None:
     """The handle carries the cost functor's M-estimator (toa_set_loss): set it from the model before every launch."""
     # SE3Reproj carries its loss in the data header: a model without one runs the kernels without the M-estimator branch (toa_tuning::
     # se3_reproj_header_l2; fp64: 308 -> 216 registers) — the field follows the model, a host call only when it changes
-    want = 1 if getattr(cost, "header_l2", False) else 0
+    want = 1 if cost.header_l2 else 0
     if getattr(ctx, "_se3_l2", 0) != want:
         ctx.set_tuning(**{**ctx.get_tuning(), "se3_reproj_header_l2": want})
-    kind = getattr(cost, "loss", None)
+    kind = cost.loss
     if kind is None:
         check(ctx.lib.toa_set_loss(ctx.h, 0, 0.0))
     else:
@@ -467,7 +574,7 @@ class DenseRow(_LossMixin):
         return DenseRow(packed, n, m, P), x0, xstar
 
 
-class GaussianPrior:
+class GaussianPrior(_Model):
     """Device residual model  r = (x - y) / sigma  (m = n) — the residual of the reference's published dense
     benchmark with the semantics of its manual Accumulate callback (benchmarks/dense.cpp:57-66):
     grad = J*res, H.diagonal() = sigma^-2, cost = res.squaredNorm() returned as a scalar (1 residual)."""
@@ -485,7 +592,7 @@ class GaussianPrior:
         return 2 * self.n * self.packed.element_size()
 
 
-class Sqrt2:
+class Sqrt2(_Model):
     """Device residual model  r = x*x - 2  (n = m = 1), tests/sqrt2.cpp:30-70."""
     model_id = MODEL_SQRT2
 
@@ -498,7 +605,7 @@ class Sqrt2:
         return 0
 
 
-class SE3Reproj:
+class SE3Reproj(_Model):
     """Device residual model: pinhole reprojection of 3-D points under an SE3 pose.
     x is [P, 12] (rotation matrix row-major + translation); the tangent has n = 6 (upsilon, omega) and the update
     is the right-multiplicative  pose <- pose * exp(delta)  of include/tinyopt/3rdparty/traits/sophus.h:24-26.
@@ -548,7 +655,7 @@ class BundleAdjustmentLists(_LossMixin):
     ``BundleAdjustment`` ([P, 12 C + 3 N]); the observations are a list sorted by (point, camera):
     intr [P, 4] = (f, cx, cy, 0), obs_cam / obs_pt [P, M] int32, obs_uv [P, M, 2].  ``Options.max_duration_ms`` is honoured.
     ``.with_loss("huber", th)`` puts every observation's squared reprojection error through an M-estimator (round 4)."""
-    model_id = None
+    route = "ba_lists"
 
     def __init__(self, intr: torch.Tensor, obs_cam: torch.Tensor, obs_pt: torch.Tensor, obs_uv: torch.Tensor, ncam: int, npts: int):
         assert intr.dim() == 2 and intr.shape[1] == 4 and intr.is_cuda
@@ -655,7 +762,6 @@ class JitResidual:
         is the body of ``template <class S> void plus(const T* x, const S* d, S* xp)``: xp = x (+) d, written over the scalar type
         like the residual — the update and the roll-back run it on plain T, the differentiation on Jets seeded on d at d = 0.
         Round 6: at every n (beyond 12 parameters: up to 64 stored scalars; ``kind="accumulate"`` bodies fill J over the tangent)."""
-        from ._capi import ToaJitSpec
         self.ctx = ctx or default_context()
         self.n, self.kR, self.kD, self.kH, self.dtype = int(n), int(residuals_per_item), int(item_scalars), int(header_scalars), dtype
         self.manifold, self.kind = manifold, kind
@@ -754,10 +860,8 @@ class JitResidual:
             pass
 
 
-class JitModel(_LossMixin, _PriorMixin, _BoundsMixin):
+class JitModel(_JitBatch):
     """A JitResidual bound to its problem data ([P][header | items x item_scalars], the layout of the built-in Jet families)."""
-    model_id = None
-
     def __init__(self, res: JitResidual, data: Optional[torch.Tensor], header: Optional[torch.Tensor] = None, items: int = 1):
         if data is None:   # a functor whose items carry no data of their own (item_scalars = 0): `items` evaluations of the header
             assert res.kD == 0 and header is not None
@@ -775,6 +879,9 @@ class JitModel(_LossMixin, _PriorMixin, _BoundsMixin):
 
     def _prior_device(self):
         return self.packed.device
+
+    def _head(self, ctx: "Context", x: torch.Tensor) -> tuple:
+        return (ctx.h, self.res._h, self.items, x.shape[0], self.packed.data_ptr(), x.data_ptr())
 
     @property
     def algorithmic_bytes_per_pass(self) -> int:
@@ -810,13 +917,13 @@ def ragged_offsets(counts=None, offsets=None, total_items: Optional[int] = None)
     return off
 
 
-class RaggedJitModel(_LossMixin, _PriorMixin, _BoundsMixin):
+class RaggedJitModel(_JitBatch):
     """A JitResidual bound to a RAGGED batch: data [total_items, item_scalars] (the items of all problems, one after another), a
     separate header [P, header_scalars] and int64 offsets [P + 1].  Taken by ``Optimize`` (LM, GN; GradientDescent for cost kinds),
     ``accumulate``, ``Eval`` and ``CalculateJac``; every problem computes bit for bit what it would alone in a uniform batch of
     its own count.  No ``splits``, no host controls (stop callbacks, max_duration_ms, the log line), no ``Optimizer`` (stepping)
     and no ``CheckGradient``: a ragged batch runs in the one-launch form only."""
-    model_id = None
+    ragged, _plain = True, (True, None)
 
     def __init__(self, res: JitResidual, data: torch.Tensor, counts=None, offsets=None, header: Optional[torch.Tensor] = None):
         if data.dim() != 2 or data.shape[1] != res.kD or not data.is_cuda or data.dtype != res.dtype:
@@ -854,15 +961,12 @@ class RaggedJitModel(_LossMixin, _PriorMixin, _BoundsMixin):
     def _prior_device(self):
         return self.data.device
 
-    def _ragged_args(self):
-        return (self.offsets.data_ptr(), self.header.data_ptr() if self.header is not None else None, self.max_items, self.total_items)
+    def _head(self, ctx: "Context", x: torch.Tensor) -> tuple:
+        return (ctx.h, self.res._h, self.offsets.data_ptr(), self.header.data_ptr() if self.header is not None else None, self.max_items,
+                self.total_items, x.shape[0], self.data.data_ptr(), x.data_ptr())
 
 
-def _refuse_ragged(what: str):
-    raise ValueError(f"a ragged batch (bind_ragged) runs in the one-launch form only: {what}")
-
-
-class SE3Prior:
+class SE3Prior(_Model):
     """SE3 pose prior — the reference's own manifold test (tests/sophus.cpp:26-44): residual(x) = log(prior_inv * x),
     differentiated on the device by dual numbers over the right perturbation (optimize_autodiff.h:48-77, sophus.h:24-26).
     prior_inv: [P, 12] (rotation matrix row-major + translation); x: [P, 12], updated by pose <- pose * exp(delta)."""
@@ -879,7 +983,7 @@ class SE3Prior:
         return 12 * self.packed.element_size()
 
 
-class MahaPrior:
+class MahaPrior(_Model):
     """Gaussian prior with a GENERAL covariance per problem: res = U (x - y) with U the upper Cholesky factor of the
     information matrix (the reference's MahaWhitenedInfoU, losses/mahalanobis.h:160-171; tests/cov.cpp:91-146).
     y: [P, n]; U: [P, n, n] upper triangular.  H = U^T U = cov^-1, so Output.Covariance() returns the prior covariance."""
@@ -903,7 +1007,7 @@ class MahaPrior:
         return (self.n + self.n * self.n) * self.packed.element_size()
 
 
-class TestFn:
+class TestFn(_Model):
     """The analytic functions of the reference's optimizer tests (tests/optimize_easy.cpp, tests/optimize_hard.cpp) as
     manual Accumulate callbacks with their exact Hessians: "rosenbrock", "plateau", "powell" (n = 4), "beale",
     "himmelblau".  x: [P, n] is a batch of starting points.  Exercises the bad-step / failed-solve / rollback
@@ -937,7 +1041,7 @@ class DenseRowAD6(_LossMixin):
         return self.m * 7 * self.packed.element_size()
 
 
-class DenseRowAD:
+class DenseRowAD(_Model):
     """The DenseRow residual for a WIDE parameter block written the tinyopt way — residual only, the Jacobian by device
     AD in the matrix cores' operand layout (csrc/row_model.hpp RowModel over AdRowFunctor, "chunked Jets").  n = 12 or n = 50.
     A: [P, m, n], b: [P, m] (natural layout)."""
@@ -960,7 +1064,7 @@ class BundleAdjustment(_LossMixin):
     complement on the reduced camera system, `toa_ba_run`); the reference would run Optimize on the full dense /
     SimplicialLDLT system (math.h:232-277).  Output.final_hessian is not produced.  ``.with_loss("cauchy", th)``: every
     observation's squared reprojection error through an M-estimator (losses/robust_norms.h:32-316; round 4)."""
-    model_id = None
+    route = "ba"
 
     def __init__(self, data: torch.Tensor, ncam: int, npts: int):
         assert data.dim() == 2 and data.shape[1] == 8 + 3 * ncam * npts and data.is_cuda
@@ -995,9 +1099,6 @@ class DenseRowNatural(_LossMixin):
     @property
     def algorithmic_bytes_per_pass(self) -> int:
         return self.m * (self.n + 1) * self.packed.element_size()
-
-
-_MODELS = (BundleAdjustmentLists, JitModel, RaggedJitModel, TestFn, MahaPrior, SE3Prior, DenseRow, GaussianPrior, Sqrt2, SE3Reproj, CircleFit, DenseRowAD6, DenseRowAD, DenseRowNatural, BundleAdjustment)
 
 
 @dataclass
@@ -1040,17 +1141,18 @@ class Output:
 
 
 def _check_call(x: torch.Tensor, cost):
-    if not isinstance(cost, _MODELS):
+    if not isinstance(cost, _Model):
         raise TypeError("cost must be a device model (DenseRow, GaussianPrior, Sqrt2, ...); host callables cannot run "
                         "on the GPU path")
     if not x.is_cuda or not x.is_contiguous():
         raise ValueError("x must be a contiguous GPU tensor")
     P, xd = x.shape
-    if xd != getattr(cost, "xdim", cost.n) or P != cost.P or x.dtype != cost.dtype:
+    if xd != cost.xdim or P != cost.P or x.dtype != cost.dtype:
         raise ValueError("x shape/dtype does not match the model")  # reference: std::invalid_argument
 
 
-def _alloc_output(P: int, n: int, options: Options, history: bool, dev) -> Output:
+def _alloc_output(P: int, n: int, options: Options, history: bool, dev, final_hessian: Optional[bool] = None) -> Output:
+    """``final_hessian``: whether there is room for the final Hessian; None = what options.hessian.save_last says."""
     i32 = dict(dtype=torch.int32, device=dev)
     f64 = dict(dtype=torch.float64, device=dev)
     out = Output(
@@ -1059,7 +1161,7 @@ def _alloc_output(P: int, n: int, options: Options, history: bool, dev) -> Outpu
         final_num_residuals=torch.zeros(P, **i32), final_rerr_dec=torch.zeros(P, **f64),
         counters=torch.zeros(8, dtype=torch.int64, device=dev),
         final_inlier_ratio=torch.ones(P, dtype=torch.float32, device=dev))
-    if options.hessian.save_last:
+    if options.hessian.save_last if final_hessian is None else final_hessian:
         out.final_hessian = torch.zeros(P, n, n, **f64)
     if history:
         hs = options.max_iters + 2
@@ -1087,26 +1189,26 @@ def _results_pod(out: Output) -> ToaResults:
     return res
 
 
-def _run_prologue(x: torch.Tensor, cost, n: int, options: Options, history: bool, ctx: Context, out: Optional[Output], zero_counters: bool,
-                  *, no_hessian: bool = False, gd: bool = False):
+def _run_prologue(x: torch.Tensor, cost, options: Options, history: bool, ctx: Context, out: Optional[Output], zero_counters: bool, gd_run: bool):
     """What every one-launch run does before its library call: the options as a pod, the caller's ``out`` (its counters zeroed
-    unless ``zero_counters`` is off) or a fresh one for n unknowns, the results pod over it, the cost's loss on the handle.
-    Returns (pod, out, res).  ``no_hessian``: a path that forms no final Hessian allocates none, whatever options.hessian.save_last
-    says; ``gd``: ... and hands the library none either (gradient descent, optimizer.h:313)."""
+    unless ``zero_counters`` is off) or a fresh one, the results pod over it, the cost's loss on the handle.  Returns (pod, out, res).
+    A path that forms no final Hessian (a GD run, the Schur solve of the BA families) allocates none, whatever options.hessian.save_last says."""
     pod = options.to_pod()
     if out is None:
-        if no_hessian:
-            import copy
-            options = copy.deepcopy(options)
-            options.hessian.save_last = False
-        out = _alloc_output(x.shape[0], n, options, history, x.device)
+        out = _alloc_output(x.shape[0], cost.n, options, history, x.device,
+                            options.hessian.save_last and not gd_run and cost.route in ("builtin", "jit"))
     elif zero_counters:
         out.counters.zero_()
     res = _results_pod(out)
-    if gd:
-        res.final_hessian = None
     _apply_loss(ctx, cost)
     return pod, out, res
+
+
+def _gd_pod(ctx: Context, options: Options) -> ToaGdOptions:
+    gd = ToaGdOptions()
+    ctx.lib.toa_gd_options_default(C.byref(gd))
+    gd.lr = float(options.gd.lr)
+    return gd
 
 
 def Optimize(x: torch.Tensor, cost, options: Optional[Options] = None, *, history: bool = False,
@@ -1124,149 +1226,62 @@ def Optimize(x: torch.Tensor, cost, options: Optional[Options] = None, *, histor
     """
     options = options or Options()
     _check_call(x, cost)
-    P, n = x.shape[0], cost.n
     ctx = ctx or default_context(x.device.index)
-    if isinstance(cost, RaggedJitModel):
-        return _optimize_ragged(x, cost, options, history, ctx, out, splits, zero_counters, keep_order)
-    if keep_order:
-        raise ValueError("keep_order is the queue order of a ragged batch (JitResidual.bind_ragged)")
-    if isinstance(cost, BundleAdjustment):
-        if options.has_host_controls() or splits is not None:
-            raise ValueError("BundleAdjustment runs as one launch per solve: no stop callbacks / splits")
-        pod, out, res = _run_prologue(x, cost, 1, options, history, ctx, out, zero_counters, no_hessian=True)
-        pod.save_last = 0
-        check(ctx.lib.toa_ba_run(ctx.h, _dtype_code(x.dtype), cost.ncam, cost.npts, P, cost.packed.data_ptr(), x.data_ptr(),
-                                 C.byref(pod), C.byref(res), out.counters.data_ptr()))
-        return out
-    if isinstance(cost, BundleAdjustmentLists):
-        if options.stop_callback is not None or options.stop_callback2 is not None or splits is not None:
-            raise ValueError("BundleAdjustmentLists: no stop callbacks / splits (max_duration_ms is honoured)")
-        pod, out, res = _run_prologue(x, cost, 1, options, history, ctx, out, zero_counters, no_hessian=True)
-        pod.save_last = 0
-        check(ctx.lib.toa_ba_lists_run(ctx.h, _dtype_code(x.dtype), cost.ncam, cost.npts, cost.nobs, P, cost.intr.data_ptr(),
-                                       cost.obs_cam.data_ptr(), cost.obs_pt.data_ptr(), cost.obs_uv.data_ptr(), x.data_ptr(),
-                                       C.byref(pod), C.byref(res), out.counters.data_ptr(), float(options.max_duration_ms or 0.0)))
-        return out
-    if isinstance(cost, JitModel) and cost.bounds is not None:
-        if splits is not None:
-            _refuse_bounds("no row-split form (splits)")
-        if options.has_host_controls():
-            _refuse_bounds("no stepping form, so no host controls (stop callbacks, max_duration_ms, the log line)")
-        if options.solver_type == Options.GradientDescent:
-            _refuse_bounds("no GradientDescent")
-        pod, out, res = _run_prologue(x, cost, n, options, history, ctx, out, zero_counters)
-        bd = cost._bounds_pod()
-        pr, pr_ref = cost._prior_ref()
-        check(ctx.lib.toa_jit_lm_run_bounds(ctx.h, cost.res._h, cost.items, P, cost.packed.data_ptr(), x.data_ptr(), C.byref(bd), pr_ref, C.byref(pod),
-                                            C.byref(res), out.counters.data_ptr()))
-        return out
-    if isinstance(cost, JitModel) and cost.prior is not None:
-        if splits is not None:
-            _refuse_prior("no row-split form (splits)")
-        if options.has_host_controls():
-            _refuse_prior("no stepping form, so no host controls (stop callbacks, max_duration_ms, the log line)")
-        if options.solver_type == Options.GradientDescent:
-            _refuse_prior("no GradientDescent")
-        pod, out, res = _run_prologue(x, cost, n, options, history, ctx, out, zero_counters)
-        pr = cost._prior_pod()
-        check(ctx.lib.toa_jit_lm_run_prior(ctx.h, cost.res._h, cost.items, P, cost.packed.data_ptr(), x.data_ptr(), C.byref(pr), C.byref(pod),
-                                           C.byref(res), out.counters.data_ptr()))
-        return out
-    if isinstance(cost, JitModel) and cost.res.large_n:
-        if splits is not None:
-            _refuse_large_n("no row-split form (splits): the pipeline already spreads a problem's rows over the device")
-        if options.has_host_controls():
-            _refuse_large_n("no stepping form, so no host controls (stop callbacks, max_duration_ms, the log line)")
-        if options.solver_type == Options.GradientDescent:
-            _refuse_large_n("no GradientDescent")
-        if torch.cuda.is_current_stream_capturing():
-            _refuse_large_n("no stream capture of the solve (the host enqueues its passes)")
-    if isinstance(cost, JitModel) and cost.res.diff != "ad" and (options.has_host_controls() or splits is not None):
-        raise ValueError("a numerically differentiated model (diff=...) runs as one launch per solve: no stop callbacks, max_duration_ms, "
-                         "log line or splits (it has no stepping and no row-split form)")
-    if isinstance(cost, JitModel) and cost.res.kind in JitResidual.COST_KINDS and options.solver_type == Options.GradientDescent:
-        return _optimize_gd(x, cost, options, history, ctx, out, splits, zero_counters)
-    if isinstance(cost, JitModel):
-        if options.has_host_controls():   # the stepping form of the run-time model (toa_jit_lm_begin / step / stop)
-            if splits is not None or out is not None:
-                raise ValueError("stop callbacks / max_duration_ms run through the stepping form: splits / out are not taken")
+    route = cost.route
+    host, gd = options.has_host_controls(), options.solver_type == _GRADIENT_DESCENT
+    gd_run = False
+    if host or gd or splits is not None or keep_order or cost.large_n:   # (a call with none of these has nothing to refuse)
+        asked = {"host": host, "gd": gd, "splits": splits is not None, "keep_order": keep_order,
+                 "callbacks": options.stop_callback is not None or options.stop_callback2 is not None,
+                 "out with host controls": host and (splits is not None or out is not None),
+                 "capture": cost.large_n and torch.cuda.is_current_stream_capturing()}
+        _refuse(_OPTIMIZE_REFUSES, _who(cost, gd), {what for what, yes in asked.items() if yes})
+        if host and route != "ba_lists":   # the stepping form (toa_lm_begin / toa_jit_lm_begin, step, stop)
             return _optimize_with_host_controls(x, cost, options, history, ctx)
-        pod, out, res = _run_prologue(x, cost, n, options, history, ctx, out, zero_counters)
+        # gd::Optimizer (optimizers/gd.h) on a scalar cost model: no final Hessian (optimizer.h:313)
+        gd_run = gd and route == "jit" and cost.res.kind in JitResidual.COST_KINDS
+    if gd_run and not cost.ragged:   # (the uniform GD entry asks for its defaults before the loss is set, the ragged one after: the order each had)
+        gdo = _gd_pod(ctx, options)
+    pod, out, res = _run_prologue(x, cost, options, history, ctx, out, zero_counters, gd_run)
+    if gd_run and cost.ragged:
+        gdo = _gd_pod(ctx, options)
+    lib = ctx.lib
+    if route == "builtin":   # (spelled out, not over _head: the single-problem solves pay for every tuple built here)
         if splits is None:   # the library decides (row-split for few, huge problems: P * 4 <= #CUs and m >= 512)
-            check(ctx.lib.toa_jit_lm_run(ctx.h, cost.res._h, cost.items, P, cost.packed.data_ptr(), x.data_ptr(), C.byref(pod),
-                                         C.byref(res), out.counters.data_ptr()))
+            check(lib.toa_lm_run(ctx.h, cost.model_id, _dtype_code(x.dtype), cost.n, cost.m, x.shape[0], cost.packed.data_ptr(), x.data_ptr(),
+                                 C.byref(pod), C.byref(res), out.counters.data_ptr()))
         else:                # explicit row-split execution with `splits` chunks per problem (0 = automatic count)
-            check(ctx.lib.toa_jit_lm_run_split(ctx.h, cost.res._h, cost.items, P, cost.packed.data_ptr(), x.data_ptr(), C.byref(pod),
-                                               C.byref(res), out.counters.data_ptr(), int(splits)))
+            check(lib.toa_lm_run_split(ctx.h, cost.model_id, _dtype_code(x.dtype), cost.n, cost.m, x.shape[0], cost.packed.data_ptr(), x.data_ptr(),
+                                       C.byref(pod), C.byref(res), out.counters.data_ptr(), int(splits)))
         return out
-    if options.has_host_controls():
-        if splits is not None or out is not None:
-            raise ValueError("stop callbacks / max_duration_ms run through the stepping form: splits / out are not taken")
-        return _optimize_with_host_controls(x, cost, options, history, ctx)
-    pod, out, res = _run_prologue(x, cost, n, options, history, ctx, out, zero_counters)
-    if splits is None:   # the library decides (row-split for few, huge problems)
-        check(ctx.lib.toa_lm_run(ctx.h, cost.model_id, _dtype_code(x.dtype), n, cost.m, P, cost.packed.data_ptr(),
-                                 x.data_ptr(), C.byref(pod), C.byref(res), out.counters.data_ptr()))
-    else:                # explicit row-split execution with `splits` chunks per problem (0 = automatic count)
-        check(ctx.lib.toa_lm_run_split(ctx.h, cost.model_id, _dtype_code(x.dtype), n, cost.m, P, cost.packed.data_ptr(),
-                                       x.data_ptr(), C.byref(pod), C.byref(res), out.counters.data_ptr(), int(splits)))
-    return out
-
-
-def _optimize_gd(x: torch.Tensor, cost: "JitModel", options: Options, history: bool, ctx: Context, out: Optional[Output],
-                 splits: Optional[int], zero_counters: bool) -> Output:
-    """gd::Optimizer (optimizers/gd.h) on a scalar cost model: one launch of toa_jit_gd_run.  No final Hessian (optimizer.h:313)."""
-    if options.has_host_controls():
-        raise ValueError("GradientDescent runs as one launch per solve: stop callbacks, max_duration_ms and the log line are not "
-                         "supported on this path (no stepping form for scalar costs)")
-    if splits is not None:
-        raise ValueError("GradientDescent: no row-split form (splits)")
-    from ._capi import ToaGdOptions
-    P = x.shape[0]
-    gd = ToaGdOptions()
-    ctx.lib.toa_gd_options_default(C.byref(gd))
-    gd.lr = float(options.gd.lr)
-    # (a loss on a scalar cost is refused by the library)
-    pod, out, res = _run_prologue(x, cost, cost.n, options, history, ctx, out, zero_counters, no_hessian=True, gd=True)
-    check(ctx.lib.toa_jit_gd_run(ctx.h, cost.res._h, cost.items, P, cost.packed.data_ptr(), x.data_ptr(), C.byref(pod), C.byref(gd),
-                                 C.byref(res), out.counters.data_ptr()))
-    return out
-
-
-def _optimize_ragged(x: torch.Tensor, cost: "RaggedJitModel", options: Options, history: bool, ctx: Context, out: Optional[Output],
-                     splits: Optional[int], zero_counters: bool, keep_order: bool) -> Output:
-    """One launch of toa_jit_lm_run_ragged (LM / GN) or toa_jit_gd_run_ragged (GradientDescent on a cost kind)."""
-    if splits is not None:
-        _refuse_ragged("no row-split form (splits)")
-    if options.has_host_controls():
-        _refuse_ragged("no stepping form, so no host controls (stop callbacks, max_duration_ms, the log line)")
-    if cost.bounds is not None and options.solver_type == Options.GradientDescent:
-        _refuse_bounds("no GradientDescent")
-    if cost.prior is not None and options.solver_type == Options.GradientDescent:
-        _refuse_prior("no GradientDescent")
-    P = x.shape[0]
-    gd_run = cost.res.kind in JitResidual.COST_KINDS and options.solver_type == Options.GradientDescent
-    pod, out, res = _run_prologue(x, cost, cost.n, options, history, ctx, out, zero_counters, no_hessian=gd_run, gd=gd_run)
-    flags = 1 if keep_order else 0
-    if gd_run:
-        from ._capi import ToaGdOptions
-        gd = ToaGdOptions()
-        ctx.lib.toa_gd_options_default(C.byref(gd))
-        gd.lr = float(options.gd.lr)
-        check(ctx.lib.toa_jit_gd_run_ragged(ctx.h, cost.res._h, *cost._ragged_args(), P, cost.data.data_ptr(), x.data_ptr(), C.byref(pod),
-                                            C.byref(gd), C.byref(res), out.counters.data_ptr(), flags))
-    elif cost.bounds is not None:
-        bd = cost._bounds_pod()
-        pr, pr_ref = cost._prior_ref()
-        check(ctx.lib.toa_jit_lm_run_ragged_bounds(ctx.h, cost.res._h, *cost._ragged_args(), P, cost.data.data_ptr(), x.data_ptr(), C.byref(bd), pr_ref,
-                                                   C.byref(pod), C.byref(res), out.counters.data_ptr(), flags))
-    elif cost.prior is not None:
-        pr = cost._prior_pod()
-        check(ctx.lib.toa_jit_lm_run_ragged_prior(ctx.h, cost.res._h, *cost._ragged_args(), P, cost.data.data_ptr(), x.data_ptr(), C.byref(pr),
-                                                  C.byref(pod), C.byref(res), out.counters.data_ptr(), flags))
-    else:
-        check(ctx.lib.toa_jit_lm_run_ragged(ctx.h, cost.res._h, *cost._ragged_args(), P, cost.data.data_ptr(), x.data_ptr(), C.byref(pod),
-                                            C.byref(res), out.counters.data_ptr(), flags))
+    if route == "jit" and not (gd_run or cost.ragged) and cost.bounds is None and cost.prior is None:
+        # the plain uniform run-time model, spelled out for the same reason (and the only one with a row-split form)
+        if splits is None:
+            check(lib.toa_jit_lm_run(ctx.h, cost.res._h, cost.items, x.shape[0], cost.packed.data_ptr(), x.data_ptr(),
+                                     C.byref(pod), C.byref(res), out.counters.data_ptr()))
+        else:
+            check(lib.toa_jit_lm_run_split(ctx.h, cost.res._h, cost.items, x.shape[0], cost.packed.data_ptr(), x.data_ptr(),
+                                           C.byref(pod), C.byref(res), out.counters.data_ptr(), int(splits)))
+        return out
+    run = (C.byref(pod), C.byref(res), out.counters.data_ptr())
+    if route == "jit":       # ragged, with a prior or bounds, or a GD run: the member of the family that the model's description selects
+        head = cost._head(ctx, x)
+        key, extras = cost._extras()
+        if key[0]:           # ragged: the flags come last
+            run += (1 if keep_order else 0,)
+        if gd_run:           # (a loss on a scalar cost is refused by the library)
+            res.final_hessian = None
+            check(getattr(lib, _JIT_ENTRIES["gd_run"][key])(*head, run[0], C.byref(gdo), *run[1:]))
+        else:
+            check(getattr(lib, _JIT_ENTRIES["lm_run"][key])(*(head + extras + run)))
+    else:   # the two BA families (no final Hessian: the library is told so)
+        pod.save_last = 0
+        P, xp = x.shape[0], x.data_ptr()
+        if route == "ba":
+            check(lib.toa_ba_run(ctx.h, _dtype_code(x.dtype), cost.ncam, cost.npts, P, cost.packed.data_ptr(), xp, *run))
+        else:
+            check(lib.toa_ba_lists_run(ctx.h, _dtype_code(x.dtype), cost.ncam, cost.npts, cost.nobs, P, cost.intr.data_ptr(), cost.obs_cam.data_ptr(),
+                                       cost.obs_pt.data_ptr(), cost.obs_uv.data_ptr(), xp, *run, float(options.max_duration_ms or 0.0)))
     return out
 
 
@@ -1280,16 +1295,7 @@ class Optimizer:
                  ctx: Optional[Context] = None):
         self.options = options or Options()
         _check_call(x, cost)
-        if isinstance(cost, RaggedJitModel):
-            _refuse_ragged("no stepping form (Optimizer)")
-        if getattr(cost, "bounds", None) is not None:
-            _refuse_bounds("no stepping form (Optimizer)")
-        if getattr(cost, "prior", None) is not None:
-            _refuse_prior("no stepping form (Optimizer)")
-        if isinstance(cost, JitModel) and cost.res.diff != "ad":
-            raise ValueError("a numerically differentiated model (diff=...) has no stepping form")
-        if isinstance(cost, JitModel) and cost.res.large_n:
-            _refuse_large_n("no stepping form (Optimizer)")
+        _refuse(_OPTIMIZER_REFUSES, _who(cost), ("Optimizer",))
         self.x, self.cost = x, cost
         self.ctx = ctx or default_context(x.device.index)
         self.pod = self.options.to_pod()
@@ -1300,28 +1306,19 @@ class Optimizer:
         self._state = torch.empty(max(int(nbytes), 1), dtype=torch.uint8, device=x.device)
         self._active = torch.zeros(1, dtype=torch.int32, device=x.device)
         _apply_loss(self.ctx, cost)
-        self._jit = isinstance(cost, JitModel)
-        if self._jit:
-            check(self.ctx.lib.toa_jit_lm_begin(self.ctx.h, cost.res._h, cost.items, P, cost.packed.data_ptr(), x.data_ptr(),
-                                                C.byref(self.pod), C.byref(self._res), self._state.data_ptr()))
-        else:
-            check(self.ctx.lib.toa_lm_begin(self.ctx.h, cost.model_id, _dtype_code(x.dtype), n, cost.m, P, cost.packed.data_ptr(),
-                                            x.data_ptr(), C.byref(self.pod), C.byref(self._res), self._state.data_ptr()))
+        self._entries = [getattr(self.ctx.lib, name) for name in _STEP_ENTRIES[cost.route == "jit"]]
+        check(self._entries[0](*self._args(), self._state.data_ptr()))
+
+    def _args(self) -> tuple:
+        """What begin, step and stop share: the handle, the batch, x, the options, the results."""
+        return (*self.cost._head(self.ctx, self.x), C.byref(self.pod), C.byref(self._res))
 
     def Step(self, sync: bool = True) -> Optional[int]:
         """One pass of the loop body for every running problem.  Returns how many are still running (host sync), or
         None with sync=False (stream-ordered, nothing read back)."""
-        x, cost = self.x, self.cost
         self._active.zero_()
-        _apply_loss(self.ctx, cost)
-        if self._jit:
-            check(self.ctx.lib.toa_jit_lm_step(self.ctx.h, cost.res._h, cost.items, x.shape[0], cost.packed.data_ptr(), x.data_ptr(),
-                                               C.byref(self.pod), C.byref(self._res), self.out.counters.data_ptr(),
-                                               self._state.data_ptr(), self._active.data_ptr()))
-        else:
-            check(self.ctx.lib.toa_lm_step(self.ctx.h, cost.model_id, _dtype_code(x.dtype), cost.n, cost.m, x.shape[0],
-                                           cost.packed.data_ptr(), x.data_ptr(), C.byref(self.pod), C.byref(self._res),
-                                           self.out.counters.data_ptr(), self._state.data_ptr(), self._active.data_ptr()))
+        _apply_loss(self.ctx, self.cost)
+        check(self._entries[1](*self._args(), self.out.counters.data_ptr(), self._state.data_ptr(), self._active.data_ptr()))
         return int(self._active.item()) if sync else None
 
     def __call__(self, max_iters: Optional[int] = None) -> Output:
@@ -1360,16 +1357,8 @@ class Optimizer:
     def stop(self, request: torch.Tensor) -> None:
         """End the still-running problems p with request[p] != 0 (int32, a StopReason such as kUserStopped / kTimedOut):
         their Output rows are finalised exactly as for a problem that stops by itself."""
-        x, cost = self.x, self.cost
-        request = request.to(device=x.device, dtype=torch.int32).contiguous()
-        if self._jit:
-            check(self.ctx.lib.toa_jit_lm_stop(self.ctx.h, cost.res._h, cost.items, x.shape[0], cost.packed.data_ptr(), x.data_ptr(),
-                                               C.byref(self.pod), C.byref(self._res), self.out.counters.data_ptr(),
-                                               self._state.data_ptr(), request.data_ptr()))
-            return
-        check(self.ctx.lib.toa_lm_stop(self.ctx.h, cost.model_id, _dtype_code(x.dtype), cost.n, cost.m, x.shape[0],
-                                       cost.packed.data_ptr(), x.data_ptr(), C.byref(self.pod), C.byref(self._res),
-                                       self.out.counters.data_ptr(), self._state.data_ptr(), request.data_ptr()))
+        request = request.to(device=self.x.device, dtype=torch.int32).contiguous()
+        check(self._entries[2](*self._args(), self.out.counters.data_ptr(), self._state.data_ptr(), request.data_ptr()))
 
 
 def _optimize_with_host_controls(x, cost, options: Options, history: bool, ctx: Context) -> Output:
@@ -1378,7 +1367,6 @@ def _optimize_with_host_controls(x, cost, options: Options, history: bool, ctx: 
     each problem that no numeric stop test has ended (the else-if chain of optimizer.h:519-534), and the accumulated
     wall time is checked against max_duration_ms (one clock for the batch) — kTimedOut overrides whatever reason a
     problem picked up in that same pass, as the unconditional assignment at optimizer.h:303-305 does."""
-    import time
     opt = Optimizer(x, cost, options, history=history, ctx=ctx)
     out = opt.out
     P = x.shape[0]
@@ -1483,50 +1471,18 @@ def accumulate(cost, x: torch.Tensor, want_grad: bool = True, ctx: Optional[Cont
     ctx = ctx or default_context(x.device.index)
     P, n = x.shape[0], cost.n
     dev = x.device
+    jit = cost.route == "jit"
+    want_H = want_grad and not (jit and cost.res.kind in JitResidual.COST_KINDS)   # SolverGD::Build: g and the cost, no H
     g = torch.zeros(P, n, dtype=x.dtype, device=dev) if want_grad else None
-    H = torch.zeros(P, n, n, dtype=x.dtype, device=dev) if want_grad else None
+    H = torch.zeros(P, n, n, dtype=x.dtype, device=dev) if want_H else None
     c = torch.zeros(P, dtype=torch.float64, device=dev)
     nres = torch.zeros(P, dtype=torch.int32, device=dev)
     _apply_loss(ctx, cost)
-    if getattr(cost, "bounds", None) is not None:   # (x as given; the active set applied to g and H; with the prior if there is one)
-        bd = cost._bounds_pod()
-        pr, pr_ref = cost._prior_ref()
-        gp, Hp = (g.data_ptr(), H.data_ptr()) if want_grad else (None, None)
-        if isinstance(cost, RaggedJitModel):
-            check(ctx.lib.toa_jit_accumulate_ragged_bounds(ctx.h, cost.res._h, *cost._ragged_args(), P, cost.data.data_ptr(), x.data_ptr(), C.byref(bd),
-                                                           pr_ref, int(want_grad), gp, Hp, c.data_ptr(), nres.data_ptr()))
-        else:
-            check(ctx.lib.toa_jit_accumulate_bounds(ctx.h, cost.res._h, cost.items, P, cost.packed.data_ptr(), x.data_ptr(), C.byref(bd), pr_ref,
-                                                    int(want_grad), gp, Hp, c.data_ptr(), nres.data_ptr()))
-        return g, H, c, nres
-    if getattr(cost, "prior", None) is not None:   # (never a cost kind: with_prior refuses those)
-        pr = cost._prior_pod()
-        gp, Hp = (g.data_ptr(), H.data_ptr()) if want_grad else (None, None)
-        if isinstance(cost, RaggedJitModel):
-            check(ctx.lib.toa_jit_accumulate_ragged_prior(ctx.h, cost.res._h, *cost._ragged_args(), P, cost.data.data_ptr(), x.data_ptr(), C.byref(pr),
-                                                          int(want_grad), gp, Hp, c.data_ptr(), nres.data_ptr()))
-        else:
-            check(ctx.lib.toa_jit_accumulate_prior(ctx.h, cost.res._h, cost.items, P, cost.packed.data_ptr(), x.data_ptr(), C.byref(pr),
-                                                   int(want_grad), gp, Hp, c.data_ptr(), nres.data_ptr()))
-        return g, H, c, nres
-    if isinstance(cost, RaggedJitModel):   # (a problem without items: zeros, nres = 0)
-        is_cost = cost.res.kind in JitResidual.COST_KINDS
-        check(ctx.lib.toa_jit_accumulate_ragged(ctx.h, cost.res._h, *cost._ragged_args(), P, cost.data.data_ptr(), x.data_ptr(), int(want_grad),
-                                                g.data_ptr() if want_grad else None, H.data_ptr() if want_grad and not is_cost else None,
-                                                c.data_ptr(), nres.data_ptr()))
-        return g, (None if is_cost else H), c, nres
-    if isinstance(cost, JitModel) and cost.res.kind in JitResidual.COST_KINDS:   # SolverGD::Build: g and the cost, no H
-        check(ctx.lib.toa_jit_accumulate(ctx.h, cost.res._h, cost.items, P, cost.packed.data_ptr(), x.data_ptr(), int(want_grad),
-                                         g.data_ptr() if want_grad else None, None, c.data_ptr(), nres.data_ptr()))
-        return g, None, c, nres
-    if isinstance(cost, JitModel):
-        check(ctx.lib.toa_jit_accumulate(ctx.h, cost.res._h, cost.items, P, cost.packed.data_ptr(), x.data_ptr(), int(want_grad),
-                                         g.data_ptr() if want_grad else None, H.data_ptr() if want_grad else None,
-                                         c.data_ptr(), nres.data_ptr()))
-        return g, H, c, nres
-    check(ctx.lib.toa_accumulate(ctx.h, cost.model_id, _dtype_code(x.dtype), n, cost.m, P, cost.packed.data_ptr(),
-                                 x.data_ptr(), int(want_grad), g.data_ptr() if want_grad else None,
-                                 H.data_ptr() if want_grad else None, c.data_ptr(), nres.data_ptr()))
+    # (bounds: x as given, the active set applied to g and H, with the prior if there is one; ragged: a problem without items gives zeros)
+    key, extras = cost._extras() if jit else (None, ())
+    entry = getattr(ctx.lib, _JIT_ENTRIES["accumulate"][key]) if jit else ctx.lib.toa_accumulate
+    check(entry(*cost._head(ctx, x), *extras, int(want_grad), g.data_ptr() if want_grad else None,
+                H.data_ptr() if want_H else None, c.data_ptr(), nres.data_ptr()))
     return g, H, c, nres
 
 
@@ -1549,16 +1505,9 @@ def CheckGradient(model: "JitModel", x: torch.Tensor, eps: Optional[float] = Non
     x [P, n]: the model's own derivatives against finite differences of its residuals (or cost terms) with step eps / 10.
     Residual kinds compare g = J^T r and, with ``check_H``, H = J^T J; cost kinds compare g.  ``eps`` None: the reference's default
     (1e-2 in float32, 1e-5 in float64).  The first check of a model with a (method, eps) compiles its numeric twin (then cached)."""
-    if getattr(model, "bounds", None) is not None:
-        _refuse_bounds("no CheckGradient (it checks the model's own rows: check the model without the bounds)")
-    if getattr(model, "prior", None) is not None:
-        _refuse_prior("no CheckGradient (it checks the model's own rows: check the model without the prior)")
-    if isinstance(model, RaggedJitModel):
-        _refuse_ragged("no CheckGradient (check the model on a uniform batch: JitResidual.bind)")
-    if not isinstance(model, JitModel):
+    if not isinstance(model, _JitBatch):
         raise TypeError("CheckGradient takes a bound run-time model (JitResidual.bind)")
-    if model.res.large_n:
-        _refuse_large_n("no CheckGradient (its numeric twin is a one-wavefront model of at most 63 parameters)")
+    _refuse(_CHECK_GRADIENT_REFUSES, _who(model), ("CheckGradient",))
     if method not in ("forward", "central", "fast_central"):
         raise ValueError(f"unknown method {method!r}; one of 'forward', 'central', 'fast_central'")
     _check_call(x, model)
@@ -1592,55 +1541,29 @@ def Eval(model: "JitModel", x: torch.Tensor, jac: bool = True, ctx: Optional[Con
     Not for scalar costs (``accumulate`` already returns their value and gradient) and not with a loss set.  ``res_out`` /
     ``J_out``: write into the caller's tensors (views are fine as long as they are contiguous).  The first call of a model
     compiles its Eval kernels (then cached)."""
-    if getattr(model, "bounds", None) is not None:
-        _refuse_bounds("no Eval (it returns the model's own rows: evaluate the model without the bounds)")
-    if getattr(model, "prior", None) is not None:
-        _refuse_prior("no Eval (it returns the model's own rows: evaluate the model without the prior)")
-    if isinstance(model, RaggedJitModel):   # outputs concatenated like the items: res [rows], J [rows, n]
-        _check_call(x, model)
-        ctx = ctx or default_context(x.device.index)
-        res = _eval_out(res_out, (model.rows,), x, "res_out")
-        J = _eval_out(J_out, (model.rows, model.n), x, "J_out") if jac else None
-        _apply_loss(ctx, model)
-        check(ctx.lib.toa_jit_eval_ragged(ctx.h, model.res._h, *model._ragged_args(), x.shape[0], model.data.data_ptr(), x.data_ptr(),
-                                          res.data_ptr(), J.data_ptr() if jac else None))
-        return res, J
-    if not isinstance(model, JitModel):
-        raise TypeError("Eval takes a bound run-time model (JitResidual.bind)")
-    _check_call(x, model)
-    ctx = ctx or default_context(x.device.index)
-    P = x.shape[0]
-    res = _eval_out(res_out, (P, model.m), x, "res_out")
-    J = _eval_out(J_out, (P, model.m, model.n), x, "J_out") if jac else None
-    _apply_loss(ctx, model)
-    check(ctx.lib.toa_jit_eval(ctx.h, model.res._h, model.items, P, model.packed.data_ptr(), x.data_ptr(), res.data_ptr(),
-                               J.data_ptr() if jac else None))
-    return res, J
+    return _eval("Eval", model, x, True, jac, ctx, res_out, J_out)
 
 
 def CalculateJac(model: "JitModel", x: torch.Tensor, ctx: Optional[Context] = None, *, J_out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """``diff::CalculateJac(x, f)`` (diff/auto_diff.h:120-138): the Jacobian rows J [P, m, n] alone (see ``Eval``)."""
-    if getattr(model, "bounds", None) is not None:
-        _refuse_bounds("no CalculateJac (it returns the model's own rows: evaluate the model without the bounds)")
-    if getattr(model, "prior", None) is not None:
-        _refuse_prior("no CalculateJac (it returns the model's own rows: evaluate the model without the prior)")
-    if isinstance(model, RaggedJitModel):
-        _check_call(x, model)
-        ctx = ctx or default_context(x.device.index)
-        J = _eval_out(J_out, (model.rows, model.n), x, "J_out")
-        _apply_loss(ctx, model)
-        check(ctx.lib.toa_jit_eval_ragged(ctx.h, model.res._h, *model._ragged_args(), x.shape[0], model.data.data_ptr(), x.data_ptr(),
-                                          None, J.data_ptr()))
-        return J
-    if not isinstance(model, JitModel):
-        raise TypeError("CalculateJac takes a bound run-time model (JitResidual.bind)")
+    return _eval("CalculateJac", model, x, False, True, ctx, None, J_out)[1]
+
+
+def _eval(what: str, model, x: torch.Tensor, want_res: bool, jac: bool, ctx: Optional[Context], res_out, J_out):
+    """``Eval``, and ``CalculateJac`` as the Eval that wants no residuals.  A ragged batch's outputs are concatenated like its items:
+    res [rows], J [rows, n]."""
+    if not isinstance(model, _JitBatch):
+        raise TypeError(f"{what} takes a bound run-time model (JitResidual.bind)")
+    _refuse(_ROWS_REFUSES[what], _who(model), (what,))
     _check_call(x, model)
     ctx = ctx or default_context(x.device.index)
-    P = x.shape[0]
-    J = _eval_out(J_out, (P, model.m, model.n), x, "J_out")
+    rows = (model.rows,) if model.ragged else (x.shape[0], model.m)
+    res = _eval_out(res_out, rows, x, "res_out") if want_res else None
+    J = _eval_out(J_out, (*rows, model.n), x, "J_out") if jac else None
     _apply_loss(ctx, model)
-    check(ctx.lib.toa_jit_eval(ctx.h, model.res._h, model.items, P, model.packed.data_ptr(), x.data_ptr(), None, J.data_ptr()))
-    return J
+    check(getattr(ctx.lib, _JIT_ENTRIES["eval"][model._plain])(*model._head(ctx, x), res.data_ptr() if want_res else None,
+                                                                    J.data_ptr() if jac else None))
+    return res, J
 
 
 def solve_damped(H: torch.Tensor, g: torch.Tensor, scale: float = 1.0, ctx: Optional[Context] = None):

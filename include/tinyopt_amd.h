@@ -459,6 +459,27 @@ int toa_ba_lists_run(toa_handle h, int dtype, int num_cameras, int num_points, i
                      const int32_t* obs_cam_dev, const int32_t* obs_pt_dev, const void* obs_uv_dev, void* x_dev,
                      const toa_options* options, const toa_results* results, uint64_t* counters_dev, double max_duration_ms);
 
+/* ---- bundle adjustment with cameras and points held CONSTANT (the bundle-adjustment twin of toa_bounds with
+ *      lo == hi): gauge fixing, localisation against a known map, structure-only refinement, incremental mapping.  Per scene, byte
+ *      flags cam_dev [P][C] and pt_dev [P][N]; non-zero = constant; either pointer may be NULL (nothing of that kind is constant).
+ *      Tangent order: cameras first (six entries each), then three per point.  On every Build the entries of a constant block leave
+ *      the system: their gradient entries are 0, their rows and columns of the full (6C + 3N)^2 Hessian are 0 with 1 on the diagonal
+ *      — on the undamped system, before grad_clipping, check_min_H_diag (which sees 1 there) and the damping.  The block's step is
+ *      exactly 0, and min_grad_norm2 / min_step_norm2 test the free part.  Cost, residual count, inliers and the M-estimator are
+ *      untouched: every observation still counts in the cost and contributes through whichever of its two blocks is free.  The stored
+ *      pose of a constant camera and the coordinates of a constant point are never written: bit for bit the caller's after the solve,
+ *      after roll-backs too.  A camera that sees nothing or a point nobody sees, flagged constant, behaves as constant.
+ *      Each call mirrors its twin (the same checks in the same order with the same texts, then: a NULL `constant`, pointers of
+ *      another device — TOA_E_ARG); both members NULL is the twin itself, bit for bit; P == 0 returns TOA_OK; stream-ordered, the
+ *      flags are never read by the host; toa_ba_lists_run_constant under stream capture behaves as toa_ba_lists_run does. */
+typedef struct toa_ba_constant { const uint8_t* cam_dev; const uint8_t* pt_dev; int32_t reserved[4]; } toa_ba_constant;
+int toa_ba_run_constant(toa_handle h, int dtype, int num_cameras, int num_points, int64_t P, const void* data_dev, void* x_dev,
+                        const toa_options* options, const toa_results* results, uint64_t* counters_dev, const toa_ba_constant* constant);
+int toa_ba_lists_run_constant(toa_handle h, int dtype, int num_cameras, int num_points, int num_obs, int64_t P, const void* intr_dev,
+                              const int32_t* obs_cam_dev, const int32_t* obs_pt_dev, const void* obs_uv_dev, void* x_dev,
+                              const toa_options* options, const toa_results* results, uint64_t* counters_dev, double max_duration_ms,
+                              const toa_ba_constant* constant);
+
 /* ---- run-time user functors (replaces "pass any callable": `Optimize(x, [](const auto& x) { return r(x); })`,
  *      include/tinyopt/optimize.h:16-33, optimizers/optimizer.h:145-160, docs/API.md:21-35 — the residual is a C++ template
  *      the reference differentiates with ceres::Jet when the USER's program is compiled).  A device path cannot take a host

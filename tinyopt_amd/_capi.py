@@ -91,6 +91,10 @@ class ToaBounds(C.Structure):   # include/tinyopt_amd.h toa_bounds (-inf / +inf:
     _fields_ = [("lo_dev", C.c_void_p), ("hi_dev", C.c_void_p), ("reserved", C.c_int32 * 4)]
 
 
+class ToaBaConstant(C.Structure):   # include/tinyopt_amd.h toa_ba_constant (byte flags [P][C] / [P][N], non-zero: held constant; NULL: none)
+    _fields_ = [("cam_dev", C.c_void_p), ("pt_dev", C.c_void_p), ("reserved", C.c_int32 * 4)]
+
+
 _P = C.c_void_p
 PROTOTYPES = {
     "toa_options_default": (None, [C.POINTER(ToaOptions)]),
@@ -132,6 +136,10 @@ PROTOTYPES = {
                              C.POINTER(ToaResults), _P]),
     "toa_ba_lists_run": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64, _P, _P, _P, _P, _P, C.POINTER(ToaOptions),
                                    C.POINTER(ToaResults), _P, C.c_double]),
+    "toa_ba_run_constant": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int64, _P, _P, C.POINTER(ToaOptions), C.POINTER(ToaResults), _P,
+                                      C.POINTER(ToaBaConstant)]),
+    "toa_ba_lists_run_constant": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64, _P, _P, _P, _P, _P, C.POINTER(ToaOptions),
+                                            C.POINTER(ToaResults), _P, C.c_double, C.POINTER(ToaBaConstant)]),
     "toa_model_compile": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_char_p, C.POINTER(_P), C.c_char_p, C.c_size_t]),
     "toa_abi_version": (C.c_int, []),
     "toa_device_count": (C.c_int, [C.POINTER(C.c_int)]),

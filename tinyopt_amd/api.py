@@ -22,7 +22,7 @@ import torch
 
 from . import _capi
 from ._capi import (F32, F64, MODEL_DENSE_ROW_AD, MODEL_DENSE_ROW_NATURAL, MODEL_TESTFN, MODEL_MAHA_PRIOR, MODEL_SE3_PRIOR, MODEL_CIRCLE_FIT, MODEL_DENSE_ROW, MODEL_DENSE_ROW_AD6, MODEL_GAUSSIAN_PRIOR, MODEL_SE3_REPROJ,
-                    MODEL_SQRT2, ToaBounds, ToaGdOptions, ToaJitSpec, ToaOptions, ToaPrior, ToaResults, check)
+                    MODEL_SQRT2, ToaBaConstant, ToaBounds, ToaGdOptions, ToaJitSpec, ToaOptions, ToaPrior, ToaResults, check)
 
 
 class StopReason(enum.IntEnum):  # include/tinyopt/stop_reasons.h:14-43
@@ -299,6 +299,44 @@ class _LossMixin(_Model):
         m = copy.copy(self)          # shares the device data
         m.loss, m.th = (loss if loss not in (None, "l2") else None), float(th)
         return m
+
+
+class _ConstantMixin(_Model):
+    """The two bundle-adjustment families: ``model.with_constant(cameras=..., points=...)`` holds cameras and points constant (DESIGN
+    section 17; `toa_ba_run_constant` / `toa_ba_lists_run_constant`) — gauge fixing (the first camera, or two), localisation against a
+    known map (every point), structure-only refinement (every camera), incremental mapping (the old key-frames and their points).
+    ``cameras``: bool or uint8, [P, C], or [C] for every scene of the batch; ``points``: [P, N] or [N]; non-zero = constant; None =
+    none of that kind.  A constant block's tangent entries leave the system on every Build (gradient 0, rows and columns of the
+    Hessian 0, diagonal 1, before clipping, the diagonal check and the damping), its step is exactly 0 and its stored pose / point
+    is never written: bit for bit the caller's after the solve.  Cost, residual count, inliers and the M-estimator are untouched.
+    Returns a copy that shares the device data, as ``with_loss`` does, and composes with it; a model without flags makes the calls
+    it always made."""
+    constant = None     # (camera flags [P, C] uint8 or None, point flags [P, N] uint8 or None)
+
+    def with_constant(self, cameras: Optional[torch.Tensor] = None, points: Optional[torch.Tensor] = None):
+        dev = (self.packed if self.route == "ba" else self.intr).device
+
+        def flags(t, count, what, letter):
+            if t is None:
+                return None
+            if not isinstance(t, torch.Tensor) or t.dtype not in (torch.bool, torch.uint8):
+                raise ValueError(f"with_constant: {what} must be a bool or uint8 tensor")
+            if t.dim() == 1:
+                t = t.unsqueeze(0).expand(self.P, -1)
+            if tuple(t.shape) != (self.P, count):
+                raise ValueError(f"with_constant: {what} must be [P, {letter}] = [{self.P}, {count}] or [{letter}] = [{count}], not {list(t.shape)}")
+            return t.to(device=dev, dtype=torch.uint8).contiguous()
+        cam, pts = flags(cameras, self.ncam, "cameras", "C"), flags(points, self.npts, "points", "N")
+        m = copy.copy(self)          # shares the device data
+        m.constant = None if cam is None and pts is None else (cam, pts)
+        return m
+
+    def _constant_pod(self) -> ToaBaConstant:
+        pod = ToaBaConstant()
+        cam, pts = self.constant
+        pod.cam_dev = cam.data_ptr() if cam is not None else None
+        pod.pt_dev = pts.data_ptr() if pts is not None else None
+        return pod
 
 
 class _PriorMixin(_Model):
@@ -649,12 +687,13 @@ class CircleFit(_LossMixin):
         return self.m * 2 * self.packed.element_size()
 
 
-class BundleAdjustmentLists(_LossMixin):
+class BundleAdjustmentLists(_LossMixin, _ConstantMixin):
     """Bundle adjustment with VISIBILITY LISTS (`toa_ba_lists_run`): tens to hundreds of SE3 cameras, each point observed by a
     few of them — what the reference would hand to Eigen's SimplicialLDLT (math.h:266-277; README.md:30,165-167).  Same x as
     ``BundleAdjustment`` ([P, 12 C + 3 N]); the observations are a list sorted by (point, camera):
     intr [P, 4] = (f, cx, cy, 0), obs_cam / obs_pt [P, M] int32, obs_uv [P, M, 2].  ``Options.max_duration_ms`` is honoured.
-    ``.with_loss("huber", th)`` puts every observation's squared reprojection error through an M-estimator (round 4)."""
+    ``.with_loss("huber", th)`` puts every observation's squared reprojection error through an M-estimator (round 4);
+    ``.with_constant(cameras=, points=)`` holds cameras and points constant (``_ConstantMixin``)."""
     route = "ba_lists"
 
     def __init__(self, intr: torch.Tensor, obs_cam: torch.Tensor, obs_pt: torch.Tensor, obs_uv: torch.Tensor, ncam: int, npts: int):
@@ -667,9 +706,14 @@ class BundleAdjustmentLists(_LossMixin):
         self.intr, self.obs_cam, self.obs_pt, self.obs_uv = intr.contiguous(), obs_cam.contiguous(), obs_pt.contiguous(), obs_uv.contiguous()
 
     @staticmethod
-    def from_dense(data: torch.Tensor, ncam: int, npts: int) -> "BundleAdjustmentLists":
+    def from_dense(data, ncam: Optional[int] = None, npts: Optional[int] = None) -> "BundleAdjustmentLists":
         """From ``BundleAdjustment``'s dense layout [P, 8 + 3 C N] = [f cx cy 0.. | uv (C, N, 2) | vis (C, N)]; every scene must
-        have the same number of visible observations."""
+        have the same number of visible observations.  ``data`` may be the ``BundleAdjustment`` model itself: its loss and its
+        constant cameras / points (``with_constant``) are carried over."""
+        if isinstance(data, BundleAdjustment):
+            lists = BundleAdjustmentLists.from_dense(data.packed, data.ncam, data.npts)
+            lists.loss, lists.th, lists.constant = data.loss, data.th, data.constant
+            return lists
         P = data.shape[0]
         uv = data[:, 8:8 + 2 * ncam * npts].reshape(P, ncam, npts, 2)
         vis = data[:, 8 + 2 * ncam * npts:].reshape(P, ncam, npts) != 0
@@ -1057,13 +1101,14 @@ class DenseRowAD(_Model):
         return self.m * (self.n + 1) * self.packed.element_size()
 
 
-class BundleAdjustment(_LossMixin):
+class BundleAdjustment(_LossMixin, _ConstantMixin):
     """C SE3 cameras x N 3-D points, pinhole reprojection residuals: the multi-pose problem behind
     config C5's single-pose block.  x: [P, 12*C + 3*N] = poses (rotation matrix row-major + translation) then points;
     data: [P, 8 + 3*C*N] = [f, cx, cy, 0... | uv (C, N, 2) | vis (C, N)].  Solved with the points eliminated (Schur
     complement on the reduced camera system, `toa_ba_run`); the reference would run Optimize on the full dense /
     SimplicialLDLT system (math.h:232-277).  Output.final_hessian is not produced.  ``.with_loss("cauchy", th)``: every
-    observation's squared reprojection error through an M-estimator (losses/robust_norms.h:32-316; round 4)."""
+    observation's squared reprojection error through an M-estimator (losses/robust_norms.h:32-316; round 4);
+    ``.with_constant(cameras=, points=)`` holds cameras and points constant (``_ConstantMixin``)."""
     route = "ba"
 
     def __init__(self, data: torch.Tensor, ncam: int, npts: int):
@@ -1278,10 +1323,18 @@ def Optimize(x: torch.Tensor, cost, options: Optional[Options] = None, *, histor
         pod.save_last = 0
         P, xp = x.shape[0], x.data_ptr()
         if route == "ba":
-            check(lib.toa_ba_run(ctx.h, _dtype_code(x.dtype), cost.ncam, cost.npts, P, cost.packed.data_ptr(), xp, *run))
+            head = (ctx.h, _dtype_code(x.dtype), cost.ncam, cost.npts, P, cost.packed.data_ptr(), xp, *run)
+            if cost.constant is None:
+                check(lib.toa_ba_run(*head))
+            else:            # cameras / points held constant (with_constant): the twin entry, the flags last
+                check(lib.toa_ba_run_constant(*head, C.byref(cost._constant_pod())))
         else:
-            check(lib.toa_ba_lists_run(ctx.h, _dtype_code(x.dtype), cost.ncam, cost.npts, cost.nobs, P, cost.intr.data_ptr(), cost.obs_cam.data_ptr(),
-                                       cost.obs_pt.data_ptr(), cost.obs_uv.data_ptr(), xp, *run, float(options.max_duration_ms or 0.0)))
+            head = (ctx.h, _dtype_code(x.dtype), cost.ncam, cost.npts, cost.nobs, P, cost.intr.data_ptr(), cost.obs_cam.data_ptr(),
+                    cost.obs_pt.data_ptr(), cost.obs_uv.data_ptr(), xp, *run, float(options.max_duration_ms or 0.0))
+            if cost.constant is None:
+                check(lib.toa_ba_lists_run(*head))
+            else:
+                check(lib.toa_ba_lists_run_constant(*head, C.byref(cost._constant_pod())))
     return out
 
 

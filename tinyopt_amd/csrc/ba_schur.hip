@@ -38,6 +38,8 @@ struct BaParams {
   int lds_part2;              // byte offset of a second partial-Gram buffer (n*n + 128 elements), 0 = none (LDS budget)
   int loss;                   // TOA_LOSS_* of the handle (toa_set_loss; the ROBUST instantiation of the kernel only)
   double loss_th2;
+  const unsigned char* cam_const;   // [P][C] / [P][N] byte flags, non-zero = held constant; either may be null.  Read by
+  const unsigned char* pt_const;    // the KC instantiations only (toa_ba_run_constant); appended: the plain kernels' offsets are unchanged
 };
 
 template <typename T>
@@ -202,7 +204,11 @@ __device__ __forceinline__ void ba_obs_wrows(const T* P, const T* q, const T f, 
 // Jt*res*s"): cost += l, the observation's rows of [J_c | J_p | r] scaled by sqrt(s) before the Grams, W scaled by s where it
 // is re-formed, inliers = observations with |r|^2 <= th^2 (cost.h:84-95).  A separate instantiation (its own translation unit,
 // -DTOA_BA_ROBUST_TU): the estimators' exp / log / atan2 would cost the plain kernel registers it does not have.
-template <typename T, int NBM, int THIN, bool ROBUST>
+// KC: cameras and points held constant (toa_ba_run_constant).  A constant block leaves the system at three places:
+// its Jacobian (J_c of a constant camera, J_p of a constant point) is zeroed where an observation is formed — and where W is
+// re-formed from it —, so U_c, g_c, V_j, g_pj and W come out as zeros; its diagonal becomes one before the diagonal check; and the
+// update never writes it.  A second instantiation: the plain kernel has no register to spare and keeps its instructions.
+template <typename T, int NBM, int THIN, bool ROBUST, bool KC = false>
 __global__ void __launch_bounds__(256, TOA_BA_WGS) ba_schur_kernel(const BaParams* __restrict__ prm) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -250,6 +256,11 @@ __global__ void __launch_bounds__(256, TOA_BA_WGS) ba_schur_kernel(const BaParam
   GT* Rinv = work + wk.Rinv; GT* qv = work + wk.q; GT* dp = work + wk.dp; GT* ldp = work + wk.ldp; GT* ptsb = work + wk.ptsb;
   GT* wgt = work + wk.wgt;
   const DenseRowLayout lay = DenseRowLayout::make(n, 4);
+  using GCB = const __attribute__((address_space(1))) unsigned char;
+  GCB* ccon = (KC && prm->cam_const) ? (GCB*)(prm->cam_const + size_t(p) * C) : nullptr;
+  GCB* pcon = (KC && prm->pt_const) ? (GCB*)(prm->pt_const + size_t(p) * N) : nullptr;
+  auto cam_k = [&](const int c) -> bool { if constexpr (KC) return ccon != nullptr && ccon[c] != 0; else return false; };
+  auto pt_k = [&](const int j) -> bool { if constexpr (KC) return pcon != nullptr && pcon[j] != 0; else return false; };
 
   if (wave == 0) {
     const int* src_o = reinterpret_cast<const int*>(&prm->opt);
@@ -296,6 +307,16 @@ __global__ void __launch_bounds__(256, TOA_BA_WGS) ba_schur_kernel(const BaParam
             for (int k = 0; k < 3; ++k) Jp[a][k] = T(0);
           }
           if (seen) ba_obs<T, true>(Pm, q, f, cx, cy, uv[(size_t(c) * N + j) * 2], uv[(size_t(c) * N + j) * 2 + 1], r, Jc, Jp);
+          if constexpr (KC) {   // the residual stays (cost, M-estimator); the constant block's derivative leaves
+            const bool ck = cam_k(c), pk = pt_k(j);
+#pragma unroll
+            for (int a = 0; a < 2; ++a) {
+#pragma unroll
+              for (int k = 0; k < 6; ++k) Jc[a][k] = ck ? T(0) : Jc[a][k];
+#pragma unroll
+              for (int k = 0; k < 3; ++k) Jp[a][k] = pk ? T(0) : Jp[a][k];
+            }
+          }
           T lobs = T(0);
           if constexpr (ROBUST) {
             const T n2 = r[0] * r[0] + r[1] * r[1];
@@ -413,6 +434,10 @@ __global__ void __launch_bounds__(256, TOA_BA_WGS) ba_schur_kernel(const BaParam
         for (int i = tid; i < 3 * N; i += 256) gp[i] = fmin(fmax(gp[i], -mm), mm);
       }
       for (int i = tid; i < n; i += 256) L.hd[i] = U[36 * (i / 6) + 7 * (i % 6)];   // undamped camera diagonal
+      if constexpr (KC) {   // a constant block: zero rows and columns (its Jacobian was zeroed), one on the diagonal — before the check
+        for (int i = tid; i < n; i += 256) if (cam_k(i / 6)) L.hd[i] = T(1);
+        for (int j = tid; j < N; j += 256) if (pt_k(j)) { hdp[3 * j] = T(1); hdp[3 * j + 1] = T(1); hdp[3 * j + 2] = T(1); }
+      }
       __syncthreads();
       if (opt.check_min_H_diag > 0) {  // lm.h:82-86, every diagonal entry of H
         T low = 0;
@@ -514,6 +539,7 @@ __global__ void __launch_bounds__(256, TOA_BA_WGS) ba_schur_kernel(const BaParam
             for (int b2 = 0; b2 < 3; ++b2) pv.pt[b2] = ptsb[3 * jj + b2];
             const T vs = ROBUST ? wgt[ob] : vis[ob];   // ROBUST: the observation's scale s at the build (0 = not seen)
             pv.vs = (live && cam_ok) ? vs : T(0);
+            if constexpr (KC) { if (cam_k(cam_ok ? cam_l : 0) || pt_k(jj)) pv.vs = T(0); }   // W of a constant block is zero
           } else {
 #pragma unroll
             for (int i = 0; i < NCOL; ++i) {
@@ -662,6 +688,7 @@ __global__ void __launch_bounds__(256, TOA_BA_WGS) ba_schur_kernel(const BaParam
         g2 += u3[0] * u3[0] + u3[1] * u3[1] + u3[2] * u3[2];
         T qb[3] = {T(0), T(0), T(0)};
         if constexpr (kRecomputeW) { qb[0] = ptsb[3 * j]; qb[1] = ptsb[3 * j + 1]; qb[2] = ptsb[3 * j + 2]; }
+        const bool pk = pt_k(j);
         for (int c = 0; c < C; ++c) {
           T wl[18];
           if constexpr (kRecomputeW) {   // W_cj re-formed from the observation at the point of the last build
@@ -669,7 +696,7 @@ __global__ void __launch_bounds__(256, TOA_BA_WGS) ba_schur_kernel(const BaParam
 #pragma unroll
             for (int i = 0; i < 12; ++i) Pm[i] = poses_b[12 * c + i];
             const T sobs = ROBUST ? wgt[size_t(c) * N + j] : vis[size_t(c) * N + j];
-            const bool seen = sobs != T(0);
+            const bool seen = sobs != T(0) && !(KC && (pk || cam_k(c)));
             ba_obs<T, true>(Pm, qb, f, T(0), T(0), T(0), T(0), rr, Jc, Jp);   // the Jacobians do not depend on cx, cy, u, v
 #pragma unroll
             for (int kk = 0; kk < 6; ++kk)
@@ -714,12 +741,12 @@ __global__ void __launch_bounds__(256, TOA_BA_WGS) ba_schur_kernel(const BaParam
     __syncthreads();
     const int action = flags[2];
     if (action == 1) {  // x (+)= dx: SE3 on the cameras (sophus.h:24-26), Euclidean on the points (traits.h:184-190)
-      if (tid < C) ba_se3_plus<T>(poses + 12 * tid, L.dx + 6 * tid, T(1));
+      if (tid < C && !cam_k(tid)) ba_se3_plus<T>(poses + 12 * tid, L.dx + 6 * tid, T(1));   // (a constant block is never written: the caller's bits)
       if (tid >= 64 && tid < 128) L.ldx[tid - 64] = L.dx[tid - 64];
-      for (int i = tid; i < 3 * N; i += 256) { const T d = dp[i]; pts[i] += d; ldp[i] = d; }
+      for (int i = tid; i < 3 * N; i += 256) { const T d = dp[i]; if (!pt_k(i / 3)) pts[i] += d; ldp[i] = d; }
     } else if (action == 2) {  // roll back the last step
-      if (tid < C) ba_se3_plus<T>(poses + 12 * tid, L.ldx + 6 * tid, T(-1));
-      for (int i = tid; i < 3 * N; i += 256) pts[i] -= ldp[i];
+      if (tid < C && !cam_k(tid)) ba_se3_plus<T>(poses + 12 * tid, L.ldx + 6 * tid, T(-1));
+      for (int i = tid; i < 3 * N; i += 256) if (!pt_k(i / 3)) pts[i] -= ldp[i];
     }
     __syncthreads();
     BA_TICK(6)
@@ -738,7 +765,7 @@ __global__ void __launch_bounds__(256, TOA_BA_WGS) ba_schur_kernel(const BaParam
   }
 }
 
-template <typename T, int NBM, int THIN, bool ROBUST>
+template <typename T, int NBM, int THIN, bool ROBUST, bool KC>
 int launch_ba(toa_handle h, BaParams& prm) {
   const int n = 6 * prm.C;
   size_t pw = WaveLds<T>::bytes(n);
@@ -763,36 +790,47 @@ int launch_ba(toa_handle h, BaParams& prm) {
   prm.work = h->scratch;
   static_assert(sizeof(BaParams) <= 1024, "parameter block too large");
   if (int rc = upload_params(h, &prm, sizeof(prm))) return rc;
-  auto kern = ba_schur_kernel<T, NBM, THIN, ROBUST>;
+  auto kern = ba_schur_kernel<T, NBM, THIN, ROBUST, KC>;
   if (int rc = ensure_lds_attr(h, (const void*)kern, lds)) return rc;
   hipLaunchKernelGGL(kern, dim3(unsigned(prm.P)), dim3(256), lds, h->stream, (const BaParams*)h->params_dev);
   HIP_TRY(hipGetLastError());
   return TOA_OK;
 }
 
-template <typename T, bool ROBUST>
+template <typename T, bool ROBUST, bool KC>
 int launch_ba_any(toa_handle h, BaParams& prm) {
   const DenseRowLayout lay = DenseRowLayout::make(6 * prm.C, 4);
   switch (lay.nbm * 8 + lay.thin) {
-    case 8 + 0: return launch_ba<T, 1, 0, ROBUST>(h, prm);    // C = 1, 2
-    case 8 + 3: return launch_ba<T, 1, 3, ROBUST>(h, prm);    // C = 3
-    case 16 + 0: return launch_ba<T, 2, 0, ROBUST>(h, prm);   // C = 4, 5
-    case 24 + 0: return launch_ba<T, 3, 0, ROBUST>(h, prm);   // C = 6, 7
-    case 24 + 1: return launch_ba<T, 3, 1, ROBUST>(h, prm);   // C = 8
-    case 32 + 0: return launch_ba<T, 4, 0, ROBUST>(h, prm);   // C = 9, 10
+    case 8 + 0: return launch_ba<T, 1, 0, ROBUST, KC>(h, prm);    // C = 1, 2
+    case 8 + 3: return launch_ba<T, 1, 3, ROBUST, KC>(h, prm);    // C = 3
+    case 16 + 0: return launch_ba<T, 2, 0, ROBUST, KC>(h, prm);   // C = 4, 5
+    case 24 + 0: return launch_ba<T, 3, 0, ROBUST, KC>(h, prm);   // C = 6, 7
+    case 24 + 1: return launch_ba<T, 3, 1, ROBUST, KC>(h, prm);   // C = 8
+    case 32 + 0: return launch_ba<T, 4, 0, ROBUST, KC>(h, prm);   // C = 9, 10
   }
   return toa_fail(TOA_E_UNSUPPORTED, "toa_ba_run: no kernel for this camera count");
 }
-// the ROBUST instantiations live in their own translation unit (the same source with -DTOA_BA_ROBUST_TU)
+// the ROBUST instantiations live in their own translation unit (the same source with -DTOA_BA_ROBUST_TU), and so do the ones with
+// constant blocks (-DTOA_BA_CONST_TU, and both defines for the robust ones): four objects that compile side by side
 int toa_ba_launch_robust(toa_handle h, int dtype, BaParams& prm);
-#ifdef TOA_BA_ROBUST_TU
+int toa_ba_launch_const(toa_handle h, int dtype, BaParams& prm);
+int toa_ba_launch_robust_const(toa_handle h, int dtype, BaParams& prm);
+#if defined(TOA_BA_ROBUST_TU) && defined(TOA_BA_CONST_TU)
+int toa_ba_launch_robust_const(toa_handle h, int dtype, BaParams& prm) {
+  return dtype == TOA_F32 ? launch_ba_any<float, true, true>(h, prm) : launch_ba_any<double, true, true>(h, prm);
+}
+#elif defined(TOA_BA_ROBUST_TU)
 int toa_ba_launch_robust(toa_handle h, int dtype, BaParams& prm) {
-  return dtype == TOA_F32 ? launch_ba_any<float, true>(h, prm) : launch_ba_any<double, true>(h, prm);
+  return dtype == TOA_F32 ? launch_ba_any<float, true, false>(h, prm) : launch_ba_any<double, true, false>(h, prm);
+}
+#elif defined(TOA_BA_CONST_TU)
+int toa_ba_launch_const(toa_handle h, int dtype, BaParams& prm) {
+  return dtype == TOA_F32 ? launch_ba_any<float, false, true>(h, prm) : launch_ba_any<double, false, true>(h, prm);
 }
 #endif
 
 
-#ifndef TOA_BA_ROBUST_TU   // (everything below exists once, in the plain translation unit)
+#if !defined(TOA_BA_ROBUST_TU) && !defined(TOA_BA_CONST_TU)   // (everything below exists once, in the plain translation unit)
 // =====================================================================================================================
 // Bundle adjustment with VISIBILITY LISTS (round 3): tens to hundreds of cameras, each point seen by a few of them.
 //
@@ -848,7 +886,13 @@ struct BlParams {
   void* dcall;
   int loss;                   // TOA_LOSS_* of the handle (toa_set_loss): each observation's |r|^2 through the M-estimator
   double loss_th2;
+  const unsigned char* cam_const;   // [P][C] / [P][N] byte flags, non-zero = held constant; either may be null.  Read by
+  const unsigned char* pt_const;    // the KC instantiations of bl_obs / bl_build / bl_update only (toa_ba_lists_run_constant)
 };
+// is block `i` of scene p flagged in `flags` ([P][count] bytes, may be null)
+__device__ __forceinline__ bool bl_flag(const unsigned char* flags, const long long p, const int count, const int i) {
+  return flags != nullptr && flags[size_t(p) * count + i] != 0;
+}
 
 template <typename T>
 struct BlWork {  // element offsets into a scene's scratch block (T)
@@ -966,7 +1010,11 @@ __global__ void __launch_bounds__(64) bl_init_kernel(const BlParams* __restrict_
   }
 }
 
-template <typename T>
+// KC (toa_ba_lists_run_constant): J_c of a constant camera and J_p of a constant point are stored as zeros — U_c,
+// g_c, V_j, g_pj and every W contraction of bl_point, bl_cam, bl_schur and bl_back then come out as zeros unchanged; the residual
+// (cost, inliers, the M-estimator) stays.  A second instantiation of this kernel, of bl_build and of bl_update: the plain pipeline
+// launches the instructions it always did.
+template <typename T, bool KC = false>
 __global__ void __launch_bounds__(256) bl_obs_kernel(const BlParams* __restrict__ prm) {
   const long long p = blockIdx.y;
   const int C = prm->C, N = prm->N, M = prm->M;
@@ -995,6 +1043,16 @@ __global__ void __launch_bounds__(256) bl_obs_kernel(const BlParams* __restrict_
   if (do_acc) {
     T Jc[2][6], Jp[2][3];
     ba_obs<T, true>(Pm, q, intr[0], intr[1], intr[2], uv[0], uv[1], r, Jc, Jp);
+    if constexpr (KC) {
+      const bool ck = bl_flag(prm->cam_const, p, C, cm), pk = bl_flag(prm->pt_const, p, N, pt);
+#pragma unroll
+      for (int a = 0; a < 2; ++a) {
+#pragma unroll
+        for (int k = 0; k < 6; ++k) Jc[a][k] = ck ? T(0) : Jc[a][k];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) Jp[a][k] = pk ? T(0) : Jp[a][k];
+      }
+    }
     const T n2 = r[0] * r[0] + r[1] * r[1];
     T l = n2, sq = T(1);
     if (loss != TOA_LOSS_L2) {
@@ -1117,7 +1175,7 @@ __device__ __forceinline__ T bl_block_sum(const T* arr, int count, T* red4) {
   return ba_block_sum<T>(v, red4);
 }
 
-template <typename T>
+template <typename T, bool KC = false>
 __global__ void __launch_bounds__(256) bl_build_kernel(const BlParams* __restrict__ prm) {
   __shared__ T red[8];
   __shared__ int sflag;
@@ -1152,6 +1210,11 @@ __global__ void __launch_bounds__(256) bl_build_kernel(const BlParams* __restric
       for (int i = tid; i < n; i += 256) w[wk.gc + i] = fmin(fmax(w[wk.gc + i], -mm), mm);
       for (int i = tid; i < 3 * N; i += 256) w[wk.gp + i] = fmin(fmax(w[wk.gp + i], -mm), mm);
     }
+    if constexpr (KC) {   // a constant block: its rows and columns are zero (bl_obs), its diagonal is one — before the diagonal check,
+      // which the same thread makes on the entries it writes here; bl_psolve then inverts the points' identity blocks like any other
+      for (int i = tid; i < n; i += 256) if (bl_flag(prm->cam_const, p, C, i / 6)) w[wk.Ud + i] = T(1);
+      for (int i = tid; i < 3 * N; i += 256) if (bl_flag(prm->pt_const, p, N, i / 3)) w[wk.Vd + i] = T(1);
+    }
     if (opt.check_min_H_diag > 0) {  // lm.h:82-86, every diagonal entry of H
       T low = 0;
       for (int i = tid; i < n; i += 256) low += fabs(w[wk.Ud + i]) < T(opt.check_min_H_diag) ? T(1) : T(0);
@@ -1169,7 +1232,9 @@ __global__ void __launch_bounds__(256) bl_build_kernel(const BlParams* __restric
     // load of the diagonal this loop makes anyway; there it was 0.3 % of a pass of the 64-camera benchmark.)
     const int* cs = prm->iwork + size_t(p) * ix.total + ix.cam_start;
     for (int i = tid; i < n; i += 256) {
-      const bool blind = cs[i / 6] == cs[i / 6 + 1];
+      const bool blind = cs[i / 6] == cs[i / 6 + 1] || (KC && bl_flag(prm->cam_const, p, C, i / 6));
+      // (KC, deliberate: a constant camera's diagonal stays 1 here, like a blind one's, where the yardstick damps it to 1 + lambda; a constant
+      //  point's V_j = I is damped by bl_psolve like every V_j.  Either way the block's row of the system is d * dc = 0 with d > 0: dc = 0.)
       const T u = w[wk.Ud + i];
       if (blind) w[wk.Ud + i] = T(1);
       else if (damp) w[wk.Ud + i] = T(double(u) * s);
@@ -1573,7 +1638,7 @@ __global__ void __launch_bounds__(256) bl_step_kernel(const BlParams* __restrict
 }
 
 // x (+)= dx: SE3 on the cameras (sophus.h:24-26), Euclidean on the points (traits.h:184-190); action 2 rolls the last step back
-template <typename T>
+template <typename T, bool KC = false>
 __global__ void __launch_bounds__(256) bl_update_kernel(const BlParams* __restrict__ prm) {
   const long long p = blockIdx.y;
   const int C = prm->C, N = prm->N, M = prm->M;
@@ -1585,7 +1650,8 @@ __global__ void __launch_bounds__(256) bl_update_kernel(const BlParams* __restri
   T* w = static_cast<T*>(prm->work) + size_t(p) * wk.total;
   T* X = static_cast<T*>(prm->x) + size_t(p) * (size_t(12) * C + size_t(3) * N);
   const int t = blockIdx.x * 256 + threadIdx.x;
-  if (t < C) {
+  // (KC: a constant block is never written — no pose * exp(0) round trip, no x + 0: the caller's bits)
+  if (t < C && !(KC && bl_flag(prm->cam_const, p, C, t))) {
     if (action == 1) {
       T d[6];
 #pragma unroll
@@ -1596,6 +1662,7 @@ __global__ void __launch_bounds__(256) bl_update_kernel(const BlParams* __restri
     }
   }
   for (int i = t; i < 3 * N; i += gridDim.x * 256) {
+    if constexpr (KC) { if (bl_flag(prm->pt_const, p, N, i / 3)) continue; }
     if (action == 1) { const T d = w[wk.dp + i]; X[size_t(12) * C + i] += d; w[wk.ldp + i] = d; }
     else X[size_t(12) * C + i] -= w[wk.ldp + i];
   }
@@ -1668,6 +1735,11 @@ int ba_lists_run_t(toa_handle h, int dtype, BlParams prm, double max_duration_ms
   const BlParams* dev = static_cast<const BlParams*>(h->params_dev);
   hipStream_t st = h->stream;
   const unsigned gM = unsigned((M + 255) / 256), gN = unsigned((N + 255) / 256), gX = unsigned((std::max(N * 3 / 8, C) + 255) / 256);
+  // constant blocks (toa_ba_lists_run_constant): the three kernels that know of them, in their second instantiation
+  const bool kc = prm.cam_const != nullptr || prm.pt_const != nullptr;
+  const auto k_obs = kc ? bl_obs_kernel<T, true> : bl_obs_kernel<T, false>;
+  const auto k_build = kc ? bl_build_kernel<T, true> : bl_build_kernel<T, false>;
+  const auto k_update = kc ? bl_update_kernel<T, true> : bl_update_kernel<T, false>;
   HIP_TRY(hipMemsetAsync(prm.iwork, 0, b_iwork, st));   // flags, camera counts
   hipLaunchKernelGGL(bl_index_a_kernel, dim3(gM, unsigned(P)), dim3(256), 0, st, dev);
   hipLaunchKernelGGL(bl_index_b_kernel, dim3(unsigned(P)), dim3(64), 0, st, dev);
@@ -1726,9 +1798,9 @@ int ba_lists_run_t(toa_handle h, int dtype, BlParams prm, double max_duration_ms
     }
     int* const any_slot = any_ring + slot;
     HIP_TRY(hipMemsetAsync(any_slot, 0, sizeof(int), st));
-    hipLaunchKernelGGL(bl_obs_kernel<T>, dim3(gM, unsigned(P)), dim3(256), 0, st, dev);
+    hipLaunchKernelGGL(k_obs, dim3(gM, unsigned(P)), dim3(256), 0, st, dev);
     hipLaunchKernelGGL(bl_point_cam_kernel<T>, dim3(gN + unsigned(C), unsigned(P)), dim3(256), 0, st, dev, int(gN));
-    hipLaunchKernelGGL(bl_build_kernel<T>, dim3(unsigned(P)), dim3(256), 0, st, dev);
+    hipLaunchKernelGGL(k_build, dim3(unsigned(P)), dim3(256), 0, st, dev);
     hipLaunchKernelGGL(bl_psolve_kernel<T>, dim3(gN, unsigned(P)), dim3(256), 0, st, dev);
     hipLaunchKernelGGL(bl_schur_kernel<T>, dim3(unsigned(C * split), unsigned(P)), dim3(256), 0, st, dev, split, spart, rpart);
     if (split > 1) hipLaunchKernelGGL(bl_schur_reduce_kernel<T>, dim3(unsigned(C), unsigned(P)), dim3(256), 0, st, dev, split, (const T*)spart, (const T*)rpart);
@@ -1757,7 +1829,7 @@ int ba_lists_run_t(toa_handle h, int dtype, BlParams prm, double max_duration_ms
     }
     hipLaunchKernelGGL(bl_back_kernel<T>, dim3(gN, unsigned(P)), dim3(256), 0, st, dev, (const int32_t*)ok);
     hipLaunchKernelGGL(bl_step_kernel<T>, dim3(unsigned(P)), dim3(256), 0, st, dev, (const int32_t*)ok, timed_out, any_slot);
-    hipLaunchKernelGGL(bl_update_kernel<T>, dim3(gX, unsigned(P)), dim3(256), 0, st, dev);
+    hipLaunchKernelGGL(k_update, dim3(gX, unsigned(P)), dim3(256), 0, st, dev);
     HIP_TRY(hipGetLastError());
     if (!capturing) {
       HIP_TRY(hipMemcpyAsync(&ev.host_flags[slot], any_slot, sizeof(int), hipMemcpyDeviceToHost, st));
@@ -1789,8 +1861,22 @@ int ba_lists_run_t(toa_handle h, int dtype, BlParams prm, double max_duration_ms
 
 using namespace toa;
 
-extern "C" int toa_ba_run(toa_handle h, int dtype, int num_cameras, int num_points, int64_t P, const void* data_dev, void* x_dev,
-                          const toa_options* options, const toa_results* results, uint64_t* counters_dev) {
+// `constant` of toa_ba_run_constant / toa_ba_lists_run_constant, judged after the twin's own checks
+static int check_ba_constant(toa_handle h, const char* who, const toa_ba_constant* constant) {
+  if (!constant) return toa_fail(TOA_E_ARG, std::string(who) + ": null constant");
+  for (const void* ptr : {(const void*)constant->cam_dev, (const void*)constant->pt_dev}) {   // (a query of the pointer table: no synchronisation)
+    hipPointerAttribute_t at;
+    if (!ptr) continue;
+    if (hipPointerGetAttributes(&at, ptr) != hipSuccess) { (void)hipGetLastError(); continue; }   // (not checkable)
+    if (at.type == hipMemoryTypeDevice && at.device != h->device)
+      return toa_fail(TOA_E_ARG, std::string(who) + ": the constant flags' cam_dev / pt_dev are on another device than the handle");
+  }
+  return TOA_OK;
+}
+
+// toa_ba_run and toa_ba_run_constant (who != nullptr: `constant` is judged, after everything the plain entry judges and in its words)
+static int ba_run(toa_handle h, int dtype, int num_cameras, int num_points, int64_t P, const void* data_dev, void* x_dev,
+                  const toa_options* options, const toa_results* results, uint64_t* counters_dev, const char* who, const toa_ba_constant* constant) {
   if (!h) return toa_fail(TOA_E_ARG, "null handle");
   if (dtype != TOA_F32 && dtype != TOA_F64) return toa_fail(TOA_E_ARG, "dtype must be TOA_F32 or TOA_F64");
   if (num_cameras < 1 || num_cameras > 10) return toa_fail(TOA_E_ARG, "toa_ba_run: 1 <= num_cameras <= 10 (reduced camera system of one wavefront)");
@@ -1798,6 +1884,8 @@ extern "C" int toa_ba_run(toa_handle h, int dtype, int num_cameras, int num_poin
   if (P < 0 || P > 65535) return toa_fail(TOA_E_ARG, "toa_ba_run: P must be in [0, 65535]");
   if (!data_dev || !x_dev || !results) return toa_fail(TOA_E_ARG, "toa_ba_run: null pointer");
   if (int rc = check_run_args("toa_ba_run", options, results, 0, 1, kLmOrGn)) return rc;
+  if (who)
+    if (int rc = check_ba_constant(h, who, constant)) return rc;
   if (P == 0) return TOA_OK;
   TOA_ON_DEVICE(h->device);
   BaParams prm;
@@ -1808,13 +1896,26 @@ extern "C" int toa_ba_run(toa_handle h, int dtype, int num_cameras, int num_poin
   prm.counters = reinterpret_cast<unsigned long long*>(counters_dev);
   prm.loss = h->loss;
   prm.loss_th2 = h->loss_th2;
+  if (constant && (constant->cam_dev || constant->pt_dev)) {   // (both null: the plain kernels, bit for bit)
+    prm.cam_const = constant->cam_dev; prm.pt_const = constant->pt_dev;
+    return h->loss != TOA_LOSS_L2 ? toa_ba_launch_robust_const(h, dtype, prm) : toa_ba_launch_const(h, dtype, prm);
+  }
   if (h->loss != TOA_LOSS_L2) return toa_ba_launch_robust(h, dtype, prm);   // the handle's M-estimator (toa_set_loss)
-  return dtype == TOA_F32 ? launch_ba_any<float, false>(h, prm) : launch_ba_any<double, false>(h, prm);
+  return dtype == TOA_F32 ? launch_ba_any<float, false, false>(h, prm) : launch_ba_any<double, false, false>(h, prm);
 }
 
-extern "C" int toa_ba_lists_run(toa_handle h, int dtype, int num_cameras, int num_points, int num_obs, int64_t P, const void* intr_dev,
-                                const int32_t* obs_cam_dev, const int32_t* obs_pt_dev, const void* obs_uv_dev, void* x_dev,
-                                const toa_options* options, const toa_results* results, uint64_t* counters_dev, double max_duration_ms) {
+extern "C" int toa_ba_run(toa_handle h, int dtype, int num_cameras, int num_points, int64_t P, const void* data_dev, void* x_dev,
+                          const toa_options* options, const toa_results* results, uint64_t* counters_dev) {
+  return ba_run(h, dtype, num_cameras, num_points, P, data_dev, x_dev, options, results, counters_dev, nullptr, nullptr);
+}
+extern "C" int toa_ba_run_constant(toa_handle h, int dtype, int num_cameras, int num_points, int64_t P, const void* data_dev, void* x_dev,
+                                   const toa_options* options, const toa_results* results, uint64_t* counters_dev, const toa_ba_constant* constant) {
+  return ba_run(h, dtype, num_cameras, num_points, P, data_dev, x_dev, options, results, counters_dev, "toa_ba_run_constant", constant);
+}
+
+static int ba_lists_run(toa_handle h, int dtype, int num_cameras, int num_points, int num_obs, int64_t P, const void* intr_dev,
+                        const int32_t* obs_cam_dev, const int32_t* obs_pt_dev, const void* obs_uv_dev, void* x_dev, const toa_options* options,
+                        const toa_results* results, uint64_t* counters_dev, double max_duration_ms, const char* who, const toa_ba_constant* constant) {
   if (!h) return toa_fail(TOA_E_ARG, "null handle");
   if (dtype != TOA_F32 && dtype != TOA_F64) return toa_fail(TOA_E_ARG, "dtype must be TOA_F32 or TOA_F64");
   if (num_cameras < 1 || num_cameras > 682) return toa_fail(TOA_E_ARG, "toa_ba_lists_run: 1 <= num_cameras <= 682 (reduced camera system of at most 4092 unknowns)");
@@ -1822,6 +1923,8 @@ extern "C" int toa_ba_lists_run(toa_handle h, int dtype, int num_cameras, int nu
   if (P < 0 || P > 65535) return toa_fail(TOA_E_ARG, "toa_ba_lists_run: P must be in [0, 65535]");
   if (!intr_dev || !obs_cam_dev || !obs_pt_dev || !obs_uv_dev || !x_dev || !results) return toa_fail(TOA_E_ARG, "toa_ba_lists_run: null pointer");
   if (int rc = check_run_args("toa_ba_lists_run", options, results, 0, 1, kLmOrGn)) return rc;
+  if (who)
+    if (int rc = check_ba_constant(h, who, constant)) return rc;
   if (P == 0) return TOA_OK;
   TOA_ON_DEVICE(h->device);
   BlParams prm;
@@ -1833,8 +1936,23 @@ extern "C" int toa_ba_lists_run(toa_handle h, int dtype, int num_cameras, int nu
   prm.counters = reinterpret_cast<unsigned long long*>(counters_dev);
   prm.loss = h->loss;
   prm.loss_th2 = h->loss_th2;
+  if (constant) { prm.cam_const = constant->cam_dev; prm.pt_const = constant->pt_dev; }   // (both null: the plain kernels, bit for bit)
   return dtype == TOA_F32 ? ba_lists_run_t<float>(h, dtype, prm, max_duration_ms) : ba_lists_run_t<double>(h, dtype, prm, max_duration_ms);
+}
+
+extern "C" int toa_ba_lists_run(toa_handle h, int dtype, int num_cameras, int num_points, int num_obs, int64_t P, const void* intr_dev,
+                                const int32_t* obs_cam_dev, const int32_t* obs_pt_dev, const void* obs_uv_dev, void* x_dev,
+                                const toa_options* options, const toa_results* results, uint64_t* counters_dev, double max_duration_ms) {
+  return ba_lists_run(h, dtype, num_cameras, num_points, num_obs, P, intr_dev, obs_cam_dev, obs_pt_dev, obs_uv_dev, x_dev, options, results,
+                      counters_dev, max_duration_ms, nullptr, nullptr);
+}
+extern "C" int toa_ba_lists_run_constant(toa_handle h, int dtype, int num_cameras, int num_points, int num_obs, int64_t P, const void* intr_dev,
+                                         const int32_t* obs_cam_dev, const int32_t* obs_pt_dev, const void* obs_uv_dev, void* x_dev,
+                                         const toa_options* options, const toa_results* results, uint64_t* counters_dev, double max_duration_ms,
+                                         const toa_ba_constant* constant) {
+  return ba_lists_run(h, dtype, num_cameras, num_points, num_obs, P, intr_dev, obs_cam_dev, obs_pt_dev, obs_uv_dev, x_dev, options, results,
+                      counters_dev, max_duration_ms, "toa_ba_lists_run_constant", constant);
 }
 #else
 }  // namespace toa
-#endif  // TOA_BA_ROBUST_TU
+#endif  // the plain translation unit

@@ -545,6 +545,24 @@ int toa_model_compile(toa_handle h, int dtype, int num_params, int residuals_per
  * SolverGD::Build's accumulation: g = sum_i grad c_i, cost = sum_i c_i, nres = 1; H_dev must be NULL. */
 #define TOA_JIT_COST 2
 #define TOA_JIT_COST_GRAD 3
+/* Second-order scalar cost — the reference's `f(x, grad, H) -> cost` (optimize.h:26-57 secondOrderValid; tests/optimize_easy.cpp is
+ * written in this form), run by LM / GN over the body's OWN gradient and Hessian: nothing is differentiated, and H need not be a Gram.
+ * The body sees x[j], h[k], p[k] on plain T as a TOA_JIT_COST_GRAD body does.  It assigns `c`, the item's cost term, and inside
+ * `if (want_grad) { ... }` ADDS the item's gradient to G[a] and the item's Hessian to H(a, b) for a <= b (the upper triangle with the
+ * diagonal).  H is an accessor over a per-lane register triangle of n (n + 1) / 2 scalars; a write with a > b goes to a discarded
+ * sink, so a body that fills the full symmetric matrix gives the same system.  Loops over a, b need COMPILE-TIME bounds: a triangle
+ * indexed by a loop that is not unrolled lands in scratch memory (toa_jit_model_stats: scratch_bytes).
+ * The problem's cost is sum_i c_i as ONE residual (Cost(Scalar), cost.h:22), its gradient sum_i g_i, its Hessian sum_i H_i; inlier
+ * ratio 1.  solver_type 1 (GaussNewton), or damping_init = 0, is Newton's method; an indefinite Hessian fails the factorisation and
+ * goes through BadStep; save_last returns the undamped Hessian of the last Build.
+ * Euclidean parameters, residuals_per_item = 1, diff = TOA_DIFF_DEFAULT, large_n = 0, 1 <= num_params <= 12 in fp32 and fp64 (78
+ * accumulators; the logistic body at n = 12 builds without scratch in both: 181 registers in fp32, 315 in fp64) — anything else is
+ * refused by toa_model_compile_ex with TOA_E_UNSUPPORTED and the numbers.
+ * Served: toa_jit_lm_run (solver_type 0 and 1, uniform batches, a handle without a loss), toa_jit_accumulate (g, cost, nres = 1 and,
+ * where H_dev is not NULL, the full symmetric [P][n][n] sum), toa_jit_model_stats, toa_jit_check_gradient (g only, as for the cost
+ * kinds).  Refused with TOA_E_UNSUPPORTED: solver_type 2 / toa_jit_gd_run (the reference throws for this signature too), a loss on
+ * the handle, the *_prior, *_bounds and *_ragged entries, toa_jit_lm_run_split, toa_jit_lm_begin / step / stop, toa_jit_eval. */
+#define TOA_JIT_COST_HESS 4
 /* Numerical differentiation (the reference's diff/num_diff.h: NumEval, EstimateNumJac, CreateNumDiffFunc1 / 2 with
  * Method::{kForward, kCentral, kFastCentral}): spec.diff != 0 differentiates a TOA_JIT_RESIDUAL or TOA_JIT_COST body by finite
  * differences with step spec.diff_h instead of Jets, so the body is only ever instantiated on plain T (S = T) and need not be

@@ -348,6 +348,18 @@ template <typename Scalar>
 class JitModel;
 template <typename Scalar>
 class RaggedJitModel;
+// What a body's text is (JitResidual's `kind`): the library's TOA_JIT_* by name
+enum JitKind {
+  kJitResidual = TOA_JIT_RESIDUAL, kJitAccumulate = TOA_JIT_ACCUMULATE, kJitCost = TOA_JIT_COST, kJitCostGrad = TOA_JIT_COST_GRAD,
+  kJitCostHess = TOA_JIT_COST_HESS
+};
+namespace detail {
+// What a second-order scalar cost (TOA_JIT_COST_HESS) does not take, in one sentence each
+inline void refuse_cost_hess(const char* what) {
+  throw std::invalid_argument(std::string("tinyopt_amd: a second-order scalar cost (TOA_JIT_COST_HESS) runs in the uniform one-launch form through Optimize "
+                                          "(LM / GN), Accumulate and diff::CheckGradient only: ") + what);
+}
+}  // namespace detail
 template <typename Scalar>
 class JitResidual {
  public:
@@ -363,6 +375,12 @@ class JitResidual {
   // diff: TOA_DIFF_DEFAULT (Jets, or the body's own derivatives), or TOA_DIFF_NUM_* (diff::to_pod(diff::kCentral) ...) — a TOA_JIT_RESIDUAL /
   //   TOA_JIT_COST body differentiated by finite differences with step diff_h (0 = FloatEpsilon<Scalar>), CreateNumDiffFunc1 / 2 of
   //   diff/num_diff.h: the body runs on plain Scalar only.  Euclidean; no stop callbacks / max_duration_ms / log line.
+  // kind = TOA_JIT_COST_HESS (kJitCostHess): a second-order scalar cost, the reference's `f(x, grad, H) -> cost` (optimize.h:26-57) — the body
+  //   assigns `c` and, inside `if (want_grad)`, ADDS the item's gradient to G[a] and its Hessian to H(a, b) for a <= b (a > b is discarded);
+  //   run by LM / GN (GaussNewton, or lm.damping_init = 0: Newton's method).  Euclidean, one cost term per item, 1 <= n <= 12 in float and
+  //   double; loops over a, b need compile-time bounds (H is a register triangle; stats().scratch_bytes shows a spill).  GradientDescent (the
+  //   reference throws for this signature too), with_loss, with_prior, with_bounds, bind_ragged, host controls, the stepping Optimizer and
+  //   diff::Eval / CalculateJac are refused (std::invalid_argument).
   // large_n = true: the model is compiled for the launch-per-phase pipeline of the wide problems instead of a wavefront per problem —
   //   n up to 1024 (float) / 512 (double), item_scalars up to 2048; TOA_JIT_RESIDUAL / TOA_JIT_ACCUMULATE, Euclidean, TOA_DIFF_DEFAULT.
   //   Optimize (LM / GN), Accumulate and diff::Eval / CalculateJac take it; with_loss, with_prior, with_bounds, bind_ragged, splits, the stepping
@@ -391,6 +409,7 @@ class JitResidual {
   // A RAGGED batch: counts[p] items for problem p (0 is legal: that problem ends with kSkipped); data: [sum of counts][item_scalars]
   // host scalars, the items of all problems one after another; header: [P][header_scalars] (null without a header).
   RaggedJitModel<Scalar> bind_ragged(const std::vector<int64_t>& counts, const Scalar* data, const Scalar* header = nullptr) const {
+    if (kind_ == TOA_JIT_COST_HESS) detail::refuse_cost_hess("no ragged batches (bind_ragged)");
     return RaggedJitModel<Scalar>(*this, counts, data, header);
   }
   const std::string& compile_log() const { return log_; }
@@ -444,6 +463,7 @@ class PriorTag {
 
  protected:
   void set_prior(const JitResidual<Scalar>& res, int64_t P, const Scalar* mu, const Scalar* W, int rows) {
+    if (res.kind() == TOA_JIT_COST_HESS) detail::refuse_cost_hess("no Gaussian prior (with_prior): a prior is a block of residuals, and it has none");
     if (res.kind() == TOA_JIT_COST || res.kind() == TOA_JIT_COST_GRAD)
       throw std::invalid_argument("tinyopt_amd::with_prior: a scalar cost model has no residuals to add a Gaussian prior to");
     if (res.manifold() != TOA_MANIFOLD_EUCLID)
@@ -486,6 +506,7 @@ class BoundsTag {
   void set_bounds(const JitResidual<Scalar>& res, int64_t P, const Scalar* lo, const Scalar* hi) {
     if (res.large_n())
       throw std::invalid_argument("tinyopt_amd::with_bounds: a model compiled with large_n takes no box bounds");
+    if (res.kind() == TOA_JIT_COST_HESS) detail::refuse_cost_hess("no box bounds (with_bounds): they project the Gauss-Newton system of a residual model");
     if (res.kind() == TOA_JIT_COST || res.kind() == TOA_JIT_COST_GRAD)
       throw std::invalid_argument("tinyopt_amd::with_bounds: a scalar cost model has no Gauss-Newton system to project");
     if (res.manifold() != TOA_MANIFOLD_EUCLID)
@@ -531,6 +552,7 @@ class JitModel : public LossTag, public PriorTag<Scalar>, public BoundsTag<Scala
   const Context& ctx() const { return res_->ctx(); }
   toa_jit_model jit_handle() const { return res_->handle(); }
   int diff() const { return res_->diff(); }
+  int kind() const { return res_->kind(); }   // TOA_JIT_*
 
  private:
   const JitResidual<Scalar>* res_;
@@ -668,6 +690,11 @@ BatchOutput Optimize(std::vector<Scalar>& x, const Cost& cost, const Options& op
     if (cost.diff() != TOA_DIFF_DEFAULT && options.has_host_controls())
       throw std::invalid_argument("tinyopt_amd::Optimize: a numerically differentiated model runs as one launch per solve: stop callbacks, "
                                   "max_duration_ms and the log line are not supported (it has no stepping form)");
+    if (cost.kind() == TOA_JIT_COST_HESS) {
+      if (gd) detail::refuse_cost_hess("no GradientDescent: the reference throws for f(x, grad, H) under GradientDescent too (optimize.h:59-75)");
+      if (cost.loss_kind != TOA_LOSS_L2) detail::refuse_cost_hess("no M-estimator (with_loss): a scalar cost has no residuals to robustify");
+      if (options.has_host_controls()) detail::refuse_cost_hess("no stepping form, so no host controls (stop callbacks, max_duration_ms, the log line)");
+    }
   }
   if (detail::has_bounds(cost)) {
     if (options.has_host_controls()) detail::refuse_bounds("no stepping form, so no host controls (stop callbacks, max_duration_ms, the log line)");

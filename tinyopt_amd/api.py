@@ -296,6 +296,8 @@ class _LossMixin(_Model):
             raise ValueError(f"unknown loss {loss!r}; one of {sorted(LOSS_KINDS)}")
         if loss not in (None, "l2") and self.large_n:
             _refuse_large_n("no M-estimator (with_loss): the pipeline's loss is per row, an item's is on its squared norm")
+        if loss not in (None, "l2") and _is_cost_hess(self):
+            _refuse_cost_hess("no M-estimator (with_loss): a scalar cost has no residuals to robustify")
         m = copy.copy(self)          # shares the device data
         m.loss, m.th = (loss if loss not in (None, "l2") else None), float(th)
         return m
@@ -352,6 +354,8 @@ class _PriorMixin(_Model):
         res = self.res
         if self.large_n:
             _refuse_large_n("no Gaussian prior (with_prior)")
+        if _is_cost_hess(self):
+            _refuse_cost_hess("no Gaussian prior (with_prior): a prior is a block of residuals, and it has none")
         if res.kind in JitResidual.COST_KINDS:
             _refuse_prior('a scalar cost model (kind="cost" / "cost_grad", GradientDescent) has no residuals to add a prior to')
         if res.manifold != "euclid":
@@ -404,6 +408,8 @@ class _BoundsMixin(_Model):
         res = self.res
         if self.large_n:
             _refuse_large_n("no box bounds (with_bounds)")
+        if _is_cost_hess(self):
+            _refuse_cost_hess("no box bounds (with_bounds): they project the Gauss-Newton system of a residual model")
         if res.kind in JitResidual.COST_KINDS:
             _refuse_bounds('a scalar cost model (kind="cost" / "cost_grad", GradientDescent) has no Gauss-Newton system to project')
         if res.manifold != "euclid":
@@ -479,6 +485,15 @@ def _refuse_prior(what: str):
     raise ValueError(f"a Gaussian prior (with_prior) stands beside a Euclidean residual model in the one-launch form only: {what}")
 
 
+def _refuse_cost_hess(what: str):
+    raise ValueError(f'a second-order scalar cost (kind="cost_hess") runs in the uniform one-launch form through Optimize (LM / GN), accumulate '
+                     f"and CheckGradient only: {what}")
+
+
+def _is_cost_hess(cost) -> bool:
+    return cost.route == "jit" and getattr(cost.res, "kind", None) == "cost_hess"
+
+
 def _refuse_ragged(what: str):
     raise ValueError(f"a ragged batch (bind_ragged) runs in the one-launch form only: {what}")
 
@@ -516,16 +531,20 @@ _REFUSALS = {
                          "supported on this path (no stepping form for scalar costs)",
     ("gd_cost", "splits"): "GradientDescent: no row-split form (splits)",
     ("stepping", "out with host controls"): "stop callbacks / max_duration_ms run through the stepping form: splits / out are not taken",
+    ("cost_hess", "gd"): _NO_GD + ": the reference throws for f(x, grad, H) under GradientDescent too (optimize.h:59-75)",
+    ("cost_hess", "splits"): _NO_SPLITS + ": its Hessian is no Gram of rows to split", ("cost_hess", "host"): _NO_HOST,
+    ("cost_hess", "Optimizer"): _NO_STEPPING,
+    **{("cost_hess", what): f"no {what} (it has no residual rows: accumulate returns its value, its gradient and its Hessian)" for what in ("Eval", "CalculateJac")},
 }
-_REFUSE_AS = {"ragged": _refuse_ragged, "bounds": _refuse_bounds, "prior": _refuse_prior, "large_n": _refuse_large_n}
-_OPTIMIZE_REFUSES = (("ragged", "splits"), ("ragged", "host"), ("uniform", "keep_order"), ("ba", "host"), ("ba", "splits"),
+_REFUSE_AS = {"ragged": _refuse_ragged, "bounds": _refuse_bounds, "prior": _refuse_prior, "large_n": _refuse_large_n, "cost_hess": _refuse_cost_hess}
+_OPTIMIZE_REFUSES = (("cost_hess", "gd"), ("cost_hess", "splits"), ("cost_hess", "host"), ("ragged", "splits"), ("ragged", "host"), ("uniform", "keep_order"), ("ba", "host"), ("ba", "splits"),
                      ("ba_lists", "callbacks"), ("ba_lists", "splits"),
                      ("bounds", "splits"), ("bounds", "host"), ("bounds", "gd"), ("prior", "splits"), ("prior", "host"), ("prior", "gd"),
                      ("large_n", "splits"), ("large_n", "host"), ("large_n", "gd"), ("large_n", "capture"), ("numeric", "host"), ("numeric", "splits"),
                      ("gd_cost", "host"), ("gd_cost", "splits"), ("stepping", "out with host controls"))
-_OPTIMIZER_REFUSES = tuple((who, "Optimizer") for who in ("ragged", "bounds", "prior", "numeric", "large_n"))
+_OPTIMIZER_REFUSES = tuple((who, "Optimizer") for who in ("cost_hess", "ragged", "bounds", "prior", "numeric", "large_n"))
 _CHECK_GRADIENT_REFUSES = tuple((who, "CheckGradient") for who in ("bounds", "prior", "ragged", "large_n"))
-_ROWS_REFUSES = {what: (("bounds", what), ("prior", what)) for what in ("Eval", "CalculateJac")}
+_ROWS_REFUSES = {what: (("cost_hess", what), ("bounds", what), ("prior", what)) for what in ("Eval", "CalculateJac")}
 
 
 def _who(cost, gd: bool = False) -> set:
@@ -541,6 +560,8 @@ def _who(cost, gd: bool = False) -> set:
         who.add("numeric")
     if gd and cost.route == "jit" and cost.res.kind in JitResidual.COST_KINDS:
         who.add("gd_cost")
+    if _is_cost_hess(cost):
+        who.add("cost_hess")
     if cost.route != "ba_lists":   # (it honours max_duration_ms itself; every other family goes to the stepping form for host controls)
         who.add("stepping")
     return who
@@ -777,6 +798,33 @@ class JitResidual:
       * ``kind="cost_grad"`` — ``f(x, grad) -> scalar`` (tests/unconstrained.cpp:19-42): ``c`` on plain T and, inside
         ``if (want_grad) { ... }``, the item's own gradient added to ``G[a]``.
 
+    Second-order scalar costs (the reference's ``f(x, grad, H) -> cost``, optimize.h:26-57; tests/optimize_easy.cpp is written in this
+    form) — ``kind="cost_hess"``, run by LM or GN over the body's OWN gradient and Hessian, which need not be a Gram: batched Newton
+    for logistic and Poisson regression, maximum-likelihood fits, any GLM.  The body sees ``x[j]``, ``h[k]``, ``p[k]`` on plain T as a
+    ``cost_grad`` body does; it assigns ``c``, the item's cost term, and inside ``if (want_grad) { ... }`` ADDS the item's gradient to
+    ``G[a]`` and the item's Hessian to ``H(a, b)`` for ``a <= b`` (the upper triangle with the diagonal; a write with ``a > b`` is
+    discarded, so a body that fills the full symmetric matrix gives the same system).  The problem's cost is the sum of its items'
+    terms as ONE residual, its gradient and Hessian their sums.  ``Options.GaussNewton``, or ``lm.damping_init = 0``, is Newton's
+    method; an indefinite Hessian fails the factorisation and the iteration goes through BadStep; ``hessian.save_last`` returns the
+    undamped Hessian of the last Build.  Loops over ``a``, ``b`` need COMPILE-TIME bounds: ``H`` is a triangle of n (n + 1) / 2
+    registers per lane, and a triangle indexed by a loop the compiler does not unroll lands in scratch memory
+    (``stats()["scratch_bytes"]`` shows it).  Euclidean parameters, one cost term per item, ``diff="ad"``, 1 <= n <= 12 in float32 and
+    float64.  ``Optimize`` (LM / GN), ``accumulate`` (g, the full symmetric H, cost) and ``CheckGradient`` take such a model
+    (``check_H=True`` compares the body's H with central differences of the body's own gradient); GradientDescent (the reference
+    throws for this signature too), ``with_loss``, ``with_prior``, ``with_bounds``, ``bind_ragged``, ``splits``, the stepping
+    ``Optimizer``, host controls, ``Eval`` / ``CalculateJac``, manifolds, numeric ``diff`` and ``large_n`` are refused with a
+    sentence.  Logistic regression (n = 12, an item = 12 features + the label +-1)::
+
+        newton = ta.JitResidual('''
+            T z = 0; for (int j = 0; j < 12; ++j) z += p[j] * x[j];
+            const T y = p[12], e = exp(-y * z), s = T(1) / (T(1) + e);        // sigma(y z)
+            c = log(T(1) + e);
+            if (want_grad) {
+              const T gz = -y * (T(1) - s), hz = s * (T(1) - s);
+              for (int a = 0; a < 12; ++a) { G[a] += gz * p[a]; for (int b = a; b < 12; ++b) H(a, b) += hz * p[a] * p[b]; }
+            }''', n=12, item_scalars=13, kind="cost_hess", dtype=torch.float64)
+        out = ta.Optimize(w, newton.bind(samples), ta.Options())        # samples: [P, items, 13] on the GPU
+
     Numerical differentiation (the reference's diff/num_diff.h: ``NumEval`` / ``CreateNumDiffFunc1/2``) — ``diff="forward"``,
     ``"central"`` or ``"fast_central"`` with step ``diff_h`` (0 = FloatEpsilon: 1e-4 in float32, 1e-7 in float64) differentiates a
     ``kind="residual"`` or ``kind="cost"`` body by finite differences instead of Jets: the body is only ever instantiated on the
@@ -794,8 +842,9 @@ class JitResidual:
     solve.  Without ``large_n`` a model of 64 parameters is refused as before.  ``stats()`` then describes the rows kernel."""
 
     MANIFOLDS = {"euclid": 0, "se3": 1, "user": 2}
-    KINDS = {"residual": 0, "accumulate": 1, "cost": 2, "cost_grad": 3}
-    COST_KINDS = ("cost", "cost_grad")
+    KINDS = {"residual": 0, "accumulate": 1, "cost": 2, "cost_grad": 3, "cost_hess": 4}
+    COST_KINDS = ("cost", "cost_grad")   # the first-order kinds (GradientDescent); "cost_hess" runs under LM / GN
+    COST_HESS_MAX_N = 12
     DIFFS = {"ad": 0, "forward": 1, "central": 2, "fast_central": 3}
 
     def __init__(self, body: str, n: int, item_scalars: int, residuals_per_item: int = 1, header_scalars: int = 0,
@@ -815,6 +864,18 @@ class JitResidual:
             raise ValueError(f"unknown diff {diff!r}; one of {sorted(self.DIFFS)}")
         self.diff, self.diff_h = diff, float(diff_h)
         self.large_n = bool(large_n)
+        if kind == "cost_hess":   # (the library refuses the same, toa_model_compile_ex: here before anything is compiled)
+            if manifold != "euclid":
+                _refuse_cost_hess(f"Euclidean parameters only, not manifold={manifold!r}")
+            if diff != "ad":
+                _refuse_cost_hess(f'the body brings its own derivatives, nothing is differentiated: diff="ad" only, not diff={diff!r}')
+            if self.large_n:
+                _refuse_cost_hess("no large_n (the launch-per-phase pipeline is for residual models)")
+            if self.kR != 1:
+                _refuse_cost_hess(f"an item has one cost term: residuals_per_item = 1, not {self.kR}")
+            if not 1 <= self.n <= self.COST_HESS_MAX_N:
+                _refuse_cost_hess(f"1 <= n <= {self.COST_HESS_MAX_N} in float32 and float64 (the Hessian's triangle, n (n + 1) / 2 <= 78 accumulators, is "
+                                  f"kept in registers), not n = {self.n} ({self.n * (self.n + 1) // 2} accumulators)")
         if self.large_n:   # (the library refuses the same, toa_model_compile_ex: here before anything is compiled)
             if kind in self.COST_KINDS:
                 _refuse_large_n('no scalar costs (kind="cost" / "cost_grad") and no GradientDescent')
@@ -870,6 +931,8 @@ class JitResidual:
         header: [P, header_scalars].  A count of 0 is legal (that problem ends with kSkipped, x untouched)."""
         if self.large_n:
             _refuse_large_n("no ragged batches (bind_ragged)")
+        if self.kind == "cost_hess":
+            _refuse_cost_hess("no ragged batches (bind_ragged)")
         return RaggedJitModel(self, data, counts, offsets, header)
 
     def stats_prior(self, ragged: bool = False) -> dict:
@@ -1556,7 +1619,9 @@ def CheckGradient(model: "JitModel", x: torch.Tensor, eps: Optional[float] = Non
                   ctx: Optional[Context] = None) -> GradientCheck:
     """``diff::CheckGradient`` / ``diff::CheckResidualsGradient`` (diff/gradient_check.h) for a bound run-time model of any kind, at
     x [P, n]: the model's own derivatives against finite differences of its residuals (or cost terms) with step eps / 10.
-    Residual kinds compare g = J^T r and, with ``check_H``, H = J^T J; cost kinds compare g.  ``eps`` None: the reference's default
+    Residual kinds compare g = J^T r and, with ``check_H``, H = J^T J; cost kinds compare g; ``kind="cost_hess"`` compares g and, with
+    ``check_H``, the body's H with central differences of the body's own gradient (2 n ``accumulate`` calls on shifted copies of x,
+    step eps / 10), returned as ``max_dist_H``.  ``eps`` None: the reference's default
     (1e-2 in float32, 1e-5 in float64).  The first check of a model with a (method, eps) compiles its numeric twin (then cached)."""
     if not isinstance(model, _JitBatch):
         raise TypeError("CheckGradient takes a bound run-time model (JitResidual.bind)")
@@ -1574,6 +1639,21 @@ def CheckGradient(model: "JitModel", x: torch.Tensor, eps: Optional[float] = Non
                                          JitResidual.DIFFS[method], int(bool(check_H)), dist.data_ptr(), ok.data_ptr()))
     if eps is None:
         e = 1e-2 if x.dtype == torch.float32 else 1e-5
+    if check_H and _is_cost_hess(model):
+        # The body's H against central differences of the body's OWN gradient with the checker's step eps / 10 (gradient_check.h:96,201):
+        # 2 n Accumulate calls on shifted copies of x, no device code of its own.  Column a of the numeric H is (g(x + h e_a) - g(x - h e_a)) / (2 h).
+        n, step = model.n, e / 10.0
+        H = accumulate(model, x, True, ctx)[1]
+        H_num = torch.empty_like(H)
+        for a in range(n):
+            xp, xm = x.clone(), x.clone()
+            xp[:, a] += step
+            xm[:, a] -= step
+            # (the step as the two points realise it, so that rounding x + h does not enter the quotient)
+            H_num[:, :, a] = (accumulate(model, xp, True, ctx)[0] - accumulate(model, xm, True, ctx)[0]) / (xp[:, a] - xm[:, a]).unsqueeze(1)
+        dist_H = (H - H_num).abs().reshape(P, -1).amax(dim=1).to(torch.float64)
+        dist_H = torch.where(torch.isnan(H - H_num).reshape(P, -1).any(dim=1), torch.full_like(dist_H, float("nan")), dist_H)
+        return GradientCheck((ok != 0) & (dist_H < e), dist[:, 0], dist_H, e)
     return GradientCheck(ok != 0, dist[:, 0], dist[:, 1], e)
 
 

@@ -286,7 +286,8 @@ int toa_accumulate(toa_handle h, int model, int dtype, int n, int m, int64_t P,
  *      dx_dev: [P][n] T; ok_dev: [P] int32 (1 = solved, 0 = "not positive definite" => solver failure).
  *      n <= 63: one wavefront per matrix.  64 <= n <= 128: one workgroup per matrix (blocked LDL^T, trailing updates
  *      on the matrix cores).  128 < n <= 1024 (fp64: 512), P <= 65535: one workgroup per matrix, blocked Cholesky through L2.
- *      Beyond, up to 4096 (P <= 65535): rocSOLVER batched Cholesky (potrf + potrs). */
+ *      Beyond, up to 4096 (P <= 65535): rocSOLVER batched Cholesky (potrf + potrs).
+ *      tests/test_gpu_k3.py pins every n <= 63, the pivoted fall-back at every panel edge, and that 64 <= n <= 128 refuses a singular semi-definite H. */
 int toa_solve_damped(toa_handle h, int dtype, int n, int64_t P, const void* H_dev, const void* g_dev,
                      double scale, void* dx_dev, int32_t* ok_dev);
 

@@ -70,6 +70,8 @@ def test_accumulate_matches_oracle(ta, oracle, dtype, n, m, P):
 @pytest.mark.parametrize("dtype", [np.float64, np.float32])
 @pytest.mark.parametrize("n", [1, 2, 5, 12, 33, 50, 63])
 def test_solve_damped_spd(ta, oracle, dtype, n):
+    """dx against the oracle's on well-conditioned Gram matrices.  The derived backward-error bound (n * gamma_{3n+8}), every n,
+    badly scaled matrices and the pivoted fall-back are in tests/test_gpu_k3.py (families and bound: tests/k3_cases.py)."""
     rng = np.random.default_rng(n)
     P = 7
     J = rng.uniform(-1, 1, (P, 3 * n + 2, n))

@@ -717,6 +717,36 @@ int toa_jit_eval_ragged(toa_handle h, toa_jit_model model, const int64_t* item_o
  *      built once, under the #defines of the uniform build that was kept (they fix the stage geometry, hence the bits); it carries a few
  *      registers more than its uniform twin and is NOT re-tried when it spills: look here when a ragged run is slower than expected. */
 int toa_jit_model_stats_ragged(toa_handle h, toa_jit_model m, int* wg_per_cu, int* num_regs, int* scratch_bytes);
+/*      L-BFGS (added under ABI 7): a limited-memory BFGS solve of a scalar cost model (TOA_JIT_COST / TOA_JIT_COST_GRAD, numerically
+ *      differentiated TOA_JIT_COST bodies included) with a backtracking Armijo line search; one wavefront per problem, one launch, the
+ *      queue of toa_jit_gd_run.  The state machine is DESIGN section 19: every pass is the model's accumulation (what toa_jit_accumulate
+ *      returns) at a trial point x_acc + alpha d; the trial is accepted when c <= f_acc + c1 alpha g_acc.d (compared in double), then the
+ *      pair (s, y) enters a ring of `history` pairs kept in LDS when s.y > 0, the stop tests of the LM path run on the normalised cost
+ *      (min_error, min_rerr_dec, min_grad_norm2) and d = -H g by the two-loop recursion (steepest descent scaled by 1 / max(1, |g|) when
+ *      the ring is empty or d is no descent direction); a rejected trial counts a failure and shrinks alpha.  x is ALWAYS an accepted point.
+ *      Stop reasons: those of the LM path; TOA_STOP_MIN_REL_ERROR also when a rejected trial's cost is the accepted one to min_rerr_dec,
+ *      TOA_STOP_MIN_DELTA_NORM when |alpha d|^2 < min_step_norm2.  No final Hessian is written, final_num_residuals = 1, inlier ratio 1;
+ *      check_final_cost is accepted and ignored; a ragged problem without items ends with TOA_STOP_SKIPPED, x untouched.
+ *      options->solver_type must be TOA_SOLVER_LBFGS.  Refused: residual, accumulate and TOA_JIT_COST_HESS models, large_n models, a loss
+ *      on the handle, grad_clipping != 0 (clipped gradients make y meaningless), history outside 1 .. 16, c1 or shrink outside (0, 1).
+ *      P == 0 returns TOA_OK.  The kernels are one more code object per model and form, built on first use and cached on disk: that
+ *      first call is refused under stream capture. */
+#define TOA_SOLVER_LBFGS 3
+typedef struct toa_lbfgs_options {
+  int32_t history;       /* pairs (s, y) kept, 1 .. 16; 8 */
+  float c1;              /* the Armijo constant, in (0, 1); 1e-4f */
+  float shrink;          /* alpha *= shrink after a rejected trial, in (0, 1); 0.5f */
+  int32_t reserved[5];
+} toa_lbfgs_options;
+void toa_lbfgs_options_default(toa_lbfgs_options* o);
+int toa_jit_lbfgs_run(toa_handle h, toa_jit_model model, int num_items, int64_t P, const void* data_dev, void* x_dev,
+                      const toa_options* options, const toa_lbfgs_options* lbfgs, const toa_results* results, uint64_t* counters_dev);
+int toa_jit_lbfgs_run_ragged(toa_handle h, toa_jit_model model, const int64_t* item_offsets_dev, const void* header_dev, int max_items,
+                             int64_t total_items, int64_t P, const void* data_dev, void* x_dev, const toa_options* options,
+                             const toa_lbfgs_options* lbfgs, const toa_results* results, uint64_t* counters_dev, uint32_t flags);
+/*      toa_jit_model_stats of the L-BFGS fused kernel, uniform (ragged = 0) or ragged, built on this call if it was not yet;
+ *      wg_per_cu at the default history of 8. */
+int toa_jit_model_stats_lbfgs(toa_handle h, toa_jit_model m, int ragged, int* wg_per_cu, int* num_regs, int* scratch_bytes);
 /*      A Gaussian prior beside a run-time model's items: per problem, with n = num_params and in the model's
  *      scalar type,
  *        mu_dev  [P][n]

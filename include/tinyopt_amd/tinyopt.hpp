@@ -41,7 +41,8 @@ enum StopReason : int {  // include/tinyopt/stop_reasons.h:14-43
 };
 
 struct Options {  // include/tinyopt/optimizers/options.h:18-156 (numeric knobs)
-  enum Solver { LevenbergMarquardt = 0, GaussNewton = 1, GradientDescent = 2 };   // GradientDescent: scalar cost models (TOA_JIT_COST*)
+  // GradientDescent, LBFGS: scalar cost models (TOA_JIT_COST / TOA_JIT_COST_GRAD); LBFGS: limited-memory BFGS, Armijo search (`lbfgs`)
+  enum Solver { LevenbergMarquardt = 0, GaussNewton = 1, GradientDescent = 2, LBFGS = 3 };
   Solver solver_type = LevenbergMarquardt;
   bool check_final_cost = false;
   bool use_step_quality_approx = false;
@@ -99,6 +100,20 @@ struct Options {  // include/tinyopt/optimizers/options.h:18-156 (numeric knobs)
     toa_gd_options_default(&g);
     g.lr = gd.lr;
     return g;
+  }
+
+  struct Lbfgs {   // toa_lbfgs_options: the textbook values (Nocedal & Wright, chapters 3 and 7)
+    int history = 8;       // pairs (s, y) kept, 1 .. 16
+    float c1 = 1e-4f;      // the Armijo constant, in (0, 1)
+    float shrink = 0.5f;   // alpha *= shrink after a rejected trial, in (0, 1)
+  } lbfgs;
+  toa_lbfgs_options lbfgs_pod() const {
+    toa_lbfgs_options l;
+    toa_lbfgs_options_default(&l);
+    l.history = lbfgs.history;
+    l.c1 = lbfgs.c1;
+    l.shrink = lbfgs.shrink;
+    return l;
   }
 
   toa_options to_pod() const {
@@ -686,6 +701,22 @@ BatchOutput Optimize(std::vector<Scalar>& x, const Cost& cost, const Options& op
   if (gd && options.has_host_controls())
     throw std::invalid_argument("tinyopt_amd::Optimize: GradientDescent runs as one launch per solve: stop callbacks, max_duration_ms "
                                 "and the log line are not supported on this path");
+  const bool lbfgs = options.solver_type == Options::LBFGS;
+  if (lbfgs) {   // (what is no first-order cost model, and a loss, the library refuses)
+    if (options.has_host_controls())
+      throw std::invalid_argument("tinyopt_amd::Optimize: L-BFGS runs as one launch per solve: stop callbacks, max_duration_ms and the log "
+                                  "line are not supported on this path");
+    if (options.grad_clipping != 0)
+      throw std::invalid_argument("tinyopt_amd::Optimize: L-BFGS: grad_clipping must be 0 (a clipped gradient makes the pairs' y = g - g_acc meaningless)");
+    if (options.lbfgs.history < 1 || options.lbfgs.history > 16) throw std::invalid_argument("tinyopt_amd::Optimize: L-BFGS: lbfgs.history must be in 1 .. 16");
+    if (!(options.lbfgs.c1 > 0.0f && options.lbfgs.c1 < 1.0f)) throw std::invalid_argument("tinyopt_amd::Optimize: L-BFGS: lbfgs.c1 must be in (0, 1)");
+    if (!(options.lbfgs.shrink > 0.0f && options.lbfgs.shrink < 1.0f))
+      throw std::invalid_argument("tinyopt_amd::Optimize: L-BFGS: lbfgs.shrink must be in (0, 1)");
+    if (detail::has_bounds(cost)) detail::refuse_bounds("no L-BFGS (and L-BFGS has no box bounds: this is not L-BFGS-B)");
+    if (detail::has_prior(cost)) detail::refuse_prior("no L-BFGS");
+    if constexpr (!detail::is_jit<Cost>::value && !detail::is_ragged<Cost>::value)
+      throw std::invalid_argument("tinyopt_amd::Optimize: L-BFGS (Options::LBFGS) needs a scalar cost model (a JitResidual of a cost kind)");
+  }
   if constexpr (detail::is_jit<Cost>::value) {
     if (cost.diff() != TOA_DIFF_DEFAULT && options.has_host_controls())
       throw std::invalid_argument("tinyopt_amd::Optimize: a numerically differentiated model runs as one launch per solve: stop callbacks, "
@@ -728,7 +759,7 @@ BatchOutput Optimize(std::vector<Scalar>& x, const Cost& cost, const Options& op
   r.final_rerr_dec = fr.data();
   r.final_inlier_ratio = inl.data();
   BatchOutput out;
-  const bool save_H = options.hessian.save_last && !gd;   // (no final Hessian on the first-order path: optimizer.h:313)
+  const bool save_H = options.hessian.save_last && !gd && !lbfgs;   // (no final Hessian on the first-order paths: optimizer.h:313)
   if (save_H) { fH = DeviceBuffer<double>(ctx, size_t(P) * n * n); fH.zero(); r.final_hessian = fH.data(); }
   if (history) {
     out.hist_stride = options.max_iters + 2;
@@ -745,6 +776,10 @@ BatchOutput Optimize(std::vector<Scalar>& x, const Cost& cost, const Options& op
       const toa_gd_options gpod = options.gd_pod();
       check(toa_jit_gd_run_ragged(ctx.get(), cost.ragged_handle(), cost.offsets_dev(), cost.header(), cost.max_items(), cost.total_items(), P,
                                   cost.data(), dx.data(), &pod, &gpod, &r, nullptr, flags));
+    } else if (lbfgs) {
+      const toa_lbfgs_options lpod = options.lbfgs_pod();
+      check(toa_jit_lbfgs_run_ragged(ctx.get(), cost.ragged_handle(), cost.offsets_dev(), cost.header(), cost.max_items(), cost.total_items(), P,
+                                     cost.data(), dx.data(), &pod, &lpod, &r, nullptr, flags));
     } else if (cost.has_bounds()) {
       const toa_bounds bd = cost.bounds_pod();
       const toa_prior pr = cost.has_prior() ? cost.prior_pod() : toa_prior{};
@@ -762,6 +797,9 @@ BatchOutput Optimize(std::vector<Scalar>& x, const Cost& cost, const Options& op
     if (gd) {   // gd::Optimizer on a scalar cost model (the library refuses any other model: optimize.h:59-75)
       const toa_gd_options gpod = options.gd_pod();
       check(toa_jit_gd_run(ctx.get(), cost.jit_handle(), cost.items(), P, cost.data(), dx.data(), &pod, &gpod, &r, nullptr));
+    } else if (lbfgs) {   // (the library refuses any model that is no first-order scalar cost)
+      const toa_lbfgs_options lpod = options.lbfgs_pod();
+      check(toa_jit_lbfgs_run(ctx.get(), cost.jit_handle(), cost.items(), P, cost.data(), dx.data(), &pod, &lpod, &r, nullptr));
     } else if (cost.has_bounds()) {
       const toa_bounds bd = cost.bounds_pod();
       const toa_prior pr = cost.has_prior() ? cost.prior_pod() : toa_prior{};

@@ -83,6 +83,10 @@ class ToaGdOptions(C.Structure):   # include/tinyopt_amd.h toa_gd_options (Optio
     _fields_ = [("lr", C.c_float), ("reserved", C.c_int32 * 7)]
 
 
+class ToaLbfgsOptions(C.Structure):   # include/tinyopt_amd.h toa_lbfgs_options
+    _fields_ = [("history", C.c_int32), ("c1", C.c_float), ("shrink", C.c_float), ("reserved", C.c_int32 * 5)]
+
+
 class ToaPrior(C.Structure):   # include/tinyopt_amd.h toa_prior (rows = 0: the diagonal form)
     _fields_ = [("mu_dev", C.c_void_p), ("W_dev", C.c_void_p), ("rows", C.c_int32), ("reserved", C.c_int32 * 5)]
 
@@ -179,6 +183,11 @@ PROTOTYPES = {
     "toa_jit_model_stats_bounds": (C.c_int, [_P, _P, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "toa_gd_options_default": (None, [C.POINTER(ToaGdOptions)]),
     "toa_jit_gd_run": (C.c_int, [_P, _P, C.c_int, C.c_int64, _P, _P, C.POINTER(ToaOptions), C.POINTER(ToaGdOptions), C.POINTER(ToaResults), _P]),
+    "toa_lbfgs_options_default": (None, [C.POINTER(ToaLbfgsOptions)]),
+    "toa_jit_lbfgs_run": (C.c_int, [_P, _P, C.c_int, C.c_int64, _P, _P, C.POINTER(ToaOptions), C.POINTER(ToaLbfgsOptions), C.POINTER(ToaResults), _P]),
+    "toa_jit_lbfgs_run_ragged": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int64, C.c_int64, _P, _P, C.POINTER(ToaOptions), C.POINTER(ToaLbfgsOptions),
+                                           C.POINTER(ToaResults), _P, C.c_uint32]),
+    "toa_jit_model_stats_lbfgs": (C.c_int, [_P, _P, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "toa_jit_lm_run_split": (C.c_int, [_P, _P, C.c_int, C.c_int64, _P, _P, C.POINTER(ToaOptions), C.POINTER(ToaResults), _P, C.c_int]),
     "toa_jit_lm_begin": (C.c_int, [_P, _P, C.c_int, C.c_int64, _P, _P, C.POINTER(ToaOptions), C.POINTER(ToaResults), _P]),
     "toa_jit_lm_step": (C.c_int, [_P, _P, C.c_int, C.c_int64, _P, _P, C.POINTER(ToaOptions), C.POINTER(ToaResults), _P, _P, _P]),

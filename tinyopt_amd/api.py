@@ -22,7 +22,7 @@ import torch
 
 from . import _capi
 from ._capi import (F32, F64, MODEL_DENSE_ROW_AD, MODEL_DENSE_ROW_NATURAL, MODEL_TESTFN, MODEL_MAHA_PRIOR, MODEL_SE3_PRIOR, MODEL_CIRCLE_FIT, MODEL_DENSE_ROW, MODEL_DENSE_ROW_AD6, MODEL_GAUSSIAN_PRIOR, MODEL_SE3_REPROJ,
-                    MODEL_SQRT2, ToaBaConstant, ToaBounds, ToaGdOptions, ToaJitSpec, ToaOptions, ToaPrior, ToaResults, check)
+                    MODEL_SQRT2, ToaBaConstant, ToaBounds, ToaGdOptions, ToaJitSpec, ToaLbfgsOptions, ToaOptions, ToaPrior, ToaResults, check)
 
 
 class StopReason(enum.IntEnum):  # include/tinyopt/stop_reasons.h:14-43
@@ -71,6 +71,13 @@ class _GD:  # options.h:147-154 — Options::GD
 
 
 @dataclass
+class _LBFGS:  # toa_lbfgs_options: the textbook values (Nocedal & Wright, chapters 3 and 7)
+    history: int = 8       # pairs (s, y) kept, 1 .. 16
+    c1: float = 1e-4       # the Armijo constant, in (0, 1)
+    shrink: float = 0.5    # alpha *= shrink after a rejected trial, in (0, 1)
+
+
+@dataclass
 class _Log:  # options.h:113-125 — the per-iteration log line of Optimizer_::Step (optimizer.h:463-516)
     enable: bool = False           # (the reference logs by default; a batched solve does not: one line per problem and iteration)
     e: str = "\u03b5\u00b2"          # symbol of the error in the line
@@ -94,6 +101,7 @@ class Options:
     LevenbergMarquardt = 0
     GaussNewton = 1
     GradientDescent = 2   # scalar cost models only (JitResidual kind="cost" / "cost_grad"): optimize.h:59-72
+    LBFGS = 3             # scalar cost models only: limited-memory BFGS with an Armijo line search (``lbfgs``)
     solver_type: int = 0
     check_final_cost: bool = False
     use_step_quality_approx: bool = False
@@ -113,6 +121,7 @@ class Options:
     lm: _LM = field(default_factory=_LM)
     gd: _GD = field(default_factory=_GD)
     log: _Log = field(default_factory=_Log)
+    lbfgs: _LBFGS = field(default_factory=_LBFGS)   # (not part of to_pod(): toa_lbfgs_options travels beside toa_options)
 
     def has_host_controls(self) -> bool:
         return self.max_duration_ms > 0 or self.stop_callback is not None or self.stop_callback2 is not None or self.log.enable
@@ -157,6 +166,7 @@ class Options:
 
 
 _GRADIENT_DESCENT = Options.GradientDescent
+_LBFGS_SOLVER = Options.LBFGS
 
 
 def _dtype_code(dt: torch.dtype) -> int:
@@ -464,6 +474,7 @@ _JIT_ENTRIES = {   # entry family -> (ragged, extra) -> the library entry
     "lm_run": {(False, "prior"): "toa_jit_lm_run_prior", (False, "bounds"): "toa_jit_lm_run_bounds",
                (True, None): "toa_jit_lm_run_ragged", (True, "prior"): "toa_jit_lm_run_ragged_prior", (True, "bounds"): "toa_jit_lm_run_ragged_bounds"},
     "gd_run": {(False, None): "toa_jit_gd_run", (True, None): "toa_jit_gd_run_ragged"},
+    "lbfgs_run": {(False, None): "toa_jit_lbfgs_run", (True, None): "toa_jit_lbfgs_run_ragged"},
     "accumulate": {(False, None): "toa_jit_accumulate", (False, "prior"): "toa_jit_accumulate_prior", (False, "bounds"): "toa_jit_accumulate_bounds",
                    (True, None): "toa_jit_accumulate_ragged", (True, "prior"): "toa_jit_accumulate_ragged_prior",
                    (True, "bounds"): "toa_jit_accumulate_ragged_bounds"},
@@ -534,21 +545,38 @@ _REFUSALS = {
     ("cost_hess", "gd"): _NO_GD + ": the reference throws for f(x, grad, H) under GradientDescent too (optimize.h:59-75)",
     ("cost_hess", "splits"): _NO_SPLITS + ": its Hessian is no Gram of rows to split", ("cost_hess", "host"): _NO_HOST,
     ("cost_hess", "Optimizer"): _NO_STEPPING,
+    # L-BFGS (Options.LBFGS): who may not ask for it, and what a cost model may not ask for beside it
+    ("not_cost", "lbfgs"): 'L-BFGS (Options.LBFGS) needs a scalar cost model (JitResidual kind="cost" / "cost_grad"): a residual model runs under LM / GN',
+    ("cost_hess", "lbfgs"): "no L-BFGS: it builds its own curvature from gradients; f(x, grad, H) runs under LM / GN",
+    **{(who, "lbfgs"): "no L-BFGS" for who in ("prior", "large_n")},
+    ("bounds", "lbfgs"): "no L-BFGS (and L-BFGS has no box bounds: this is not L-BFGS-B)",
+    ("lbfgs_cost", "host"): "L-BFGS runs as one launch per solve: stop callbacks, max_duration_ms and the log line are not supported on this "
+                            "path (no stepping form for scalar costs)",
+    ("lbfgs_cost", "splits"): "L-BFGS: no row-split form (splits)",
+    ("lbfgs_cost", "grad_clipping"): "L-BFGS: grad_clipping must be 0 (a clipped gradient makes the pairs' y = g - g_acc meaningless)",
+    ("lbfgs_cost", "lbfgs.history"): "L-BFGS: lbfgs.history must be in 1 .. 16",
+    ("lbfgs_cost", "lbfgs.c1"): "L-BFGS: lbfgs.c1 (the Armijo constant) must be in (0, 1)",
+    ("lbfgs_cost", "lbfgs.shrink"): "L-BFGS: lbfgs.shrink (the backtracking factor) must be in (0, 1)",
+    ("lbfgs", "Optimizer"): "L-BFGS (Options.LBFGS) has no stepping form (Optimizer): run it through Optimize",
     **{("cost_hess", what): f"no {what} (it has no residual rows: accumulate returns its value, its gradient and its Hessian)" for what in ("Eval", "CalculateJac")},
 }
 _REFUSE_AS = {"ragged": _refuse_ragged, "bounds": _refuse_bounds, "prior": _refuse_prior, "large_n": _refuse_large_n, "cost_hess": _refuse_cost_hess}
-_OPTIMIZE_REFUSES = (("cost_hess", "gd"), ("cost_hess", "splits"), ("cost_hess", "host"), ("ragged", "splits"), ("ragged", "host"), ("uniform", "keep_order"), ("ba", "host"), ("ba", "splits"),
+_OPTIMIZE_REFUSES = (("cost_hess", "lbfgs"), ("bounds", "lbfgs"), ("prior", "lbfgs"), ("large_n", "lbfgs"), ("not_cost", "lbfgs"),
+                     ("lbfgs_cost", "host"), ("lbfgs_cost", "splits"), ("lbfgs_cost", "grad_clipping"), ("lbfgs_cost", "lbfgs.history"),
+                     ("lbfgs_cost", "lbfgs.c1"), ("lbfgs_cost", "lbfgs.shrink"),
+                     ("cost_hess", "gd"), ("cost_hess", "splits"), ("cost_hess", "host"), ("ragged", "splits"), ("ragged", "host"), ("uniform", "keep_order"), ("ba", "host"), ("ba", "splits"),
                      ("ba_lists", "callbacks"), ("ba_lists", "splits"),
                      ("bounds", "splits"), ("bounds", "host"), ("bounds", "gd"), ("prior", "splits"), ("prior", "host"), ("prior", "gd"),
                      ("large_n", "splits"), ("large_n", "host"), ("large_n", "gd"), ("large_n", "capture"), ("numeric", "host"), ("numeric", "splits"),
                      ("gd_cost", "host"), ("gd_cost", "splits"), ("stepping", "out with host controls"))
-_OPTIMIZER_REFUSES = tuple((who, "Optimizer") for who in ("cost_hess", "ragged", "bounds", "prior", "numeric", "large_n"))
+_OPTIMIZER_REFUSES = tuple((who, "Optimizer") for who in ("lbfgs", "cost_hess", "ragged", "bounds", "prior", "numeric", "large_n"))
 _CHECK_GRADIENT_REFUSES = tuple((who, "CheckGradient") for who in ("bounds", "prior", "ragged", "large_n"))
 _ROWS_REFUSES = {what: (("cost_hess", what), ("bounds", what), ("prior", what)) for what in ("Eval", "CalculateJac")}
 
 
-def _who(cost, gd: bool = False) -> set:
-    """The names under which ``cost`` can refuse something (the first column of _REFUSALS); ``gd``: the options ask for GradientDescent."""
+def _who(cost, gd: bool = False, lbfgs: bool = False) -> set:
+    """The names under which ``cost`` can refuse something (the first column of _REFUSALS); ``gd`` / ``lbfgs``: the options ask for
+    GradientDescent / L-BFGS."""
     who = {cost.route, "ragged" if cost.ragged else "uniform"}
     if cost.bounds is not None:
         who.add("bounds")
@@ -560,6 +588,8 @@ def _who(cost, gd: bool = False) -> set:
         who.add("numeric")
     if gd and cost.route == "jit" and cost.res.kind in JitResidual.COST_KINDS:
         who.add("gd_cost")
+    if lbfgs:   # a first-order cost model, or anything else
+        who.add("lbfgs_cost" if cost.route == "jit" and cost.res.kind in JitResidual.COST_KINDS else "not_cost")
     if _is_cost_hess(cost):
         who.add("cost_hess")
     if cost.route != "ba_lists":   # (it honours max_duration_ms itself; every other family goes to the stepping form for host controls)
@@ -798,6 +828,13 @@ class JitResidual:
       * ``kind="cost_grad"`` — ``f(x, grad) -> scalar`` (tests/unconstrained.cpp:19-42): ``c`` on plain T and, inside
         ``if (want_grad) { ... }``, the item's own gradient added to ``G[a]``.
 
+    The same two kinds run under ``options.solver_type = Options.LBFGS``: limited-memory BFGS with a backtracking
+    Armijo search — ``options.lbfgs.history`` pairs (1 .. 16, default 8) kept in the wave's LDS, ``lbfgs.c1`` (1e-4), ``lbfgs.shrink``
+    (0.5) — for any n up to 63, uniform and ragged batches, no ``lr`` to tune and no Hessian to write down; x is always an accepted
+    point, no final Hessian.  Refused with a sentence: every other model kind, ``with_loss``, ``with_prior``, ``with_bounds`` (no
+    L-BFGS-B), ``splits``, the stepping ``Optimizer``, host controls, ``large_n``, ``grad_clipping != 0``, option values out of range.
+    ``stats_lbfgs()`` describes its kernel.
+
     Second-order scalar costs (the reference's ``f(x, grad, H) -> cost``, optimize.h:26-57; tests/optimize_easy.cpp is written in this
     form) — ``kind="cost_hess"``, run by LM or GN over the body's OWN gradient and Hessian, which need not be a Gram: batched Newton
     for logistic and Poisson regression, maximum-likelihood fits, any GLM.  The body sees ``x[j]``, ``h[k]``, ``p[k]`` on plain T as a
@@ -947,6 +984,13 @@ class JitResidual:
         plain L2 build, compiled by this call if it was not yet)."""
         v = [C.c_int(0) for _ in range(3)]
         check(self.ctx.lib.toa_jit_model_stats_bounds(self.ctx.h, self._h, int(bool(ragged)), int(bool(with_prior)), *[C.byref(t) for t in v]))
+        return dict(wg_per_cu=v[0].value, num_regs=v[1].value, scratch_bytes=v[2].value)
+
+    def stats_lbfgs(self, ragged: bool = False) -> dict:
+        """``stats_ragged`` of the L-BFGS fused kernel of a cost model (``Options.LBFGS``), uniform or ragged, compiled by this call if
+        it was not yet; ``wg_per_cu`` at the default history of 8 (the ring of pairs is LDS of the launch)."""
+        v = [C.c_int(0) for _ in range(3)]
+        check(self.ctx.lib.toa_jit_model_stats_lbfgs(self.ctx.h, self._h, int(bool(ragged)), *[C.byref(t) for t in v]))
         return dict(wg_per_cu=v[0].value, num_regs=v[1].value, scratch_bytes=v[2].value)
 
     def stats_ragged(self) -> dict:
@@ -1312,6 +1356,13 @@ def _run_prologue(x: torch.Tensor, cost, options: Options, history: bool, ctx: C
     return pod, out, res
 
 
+def _lbfgs_pod(ctx: Context, options: Options) -> ToaLbfgsOptions:
+    lb = ToaLbfgsOptions()
+    ctx.lib.toa_lbfgs_options_default(C.byref(lb))
+    lb.history, lb.c1, lb.shrink = int(options.lbfgs.history), float(options.lbfgs.c1), float(options.lbfgs.shrink)
+    return lb
+
+
 def _gd_pod(ctx: Context, options: Options) -> ToaGdOptions:
     gd = ToaGdOptions()
     ctx.lib.toa_gd_options_default(C.byref(gd))
@@ -1337,22 +1388,30 @@ def Optimize(x: torch.Tensor, cost, options: Optional[Options] = None, *, histor
     ctx = ctx or default_context(x.device.index)
     route = cost.route
     host, gd = options.has_host_controls(), options.solver_type == _GRADIENT_DESCENT
-    gd_run = False
-    if host or gd or splits is not None or keep_order or cost.large_n:   # (a call with none of these has nothing to refuse)
+    lbfgs = options.solver_type == _LBFGS_SOLVER
+    gd_run = lbfgs_run = False
+    if host or gd or lbfgs or splits is not None or keep_order or cost.large_n:   # (a call with none of these has nothing to refuse)
         asked = {"host": host, "gd": gd, "splits": splits is not None, "keep_order": keep_order,
                  "callbacks": options.stop_callback is not None or options.stop_callback2 is not None,
                  "out with host controls": host and (splits is not None or out is not None),
                  "capture": cost.large_n and torch.cuda.is_current_stream_capturing()}
-        _refuse(_OPTIMIZE_REFUSES, _who(cost, gd), {what for what, yes in asked.items() if yes})
+        if lbfgs:
+            lb = options.lbfgs
+            asked.update({"lbfgs": True, "grad_clipping": options.grad_clipping != 0, "lbfgs.history": not 1 <= int(lb.history) <= 16,
+                          "lbfgs.c1": not 0.0 < lb.c1 < 1.0, "lbfgs.shrink": not 0.0 < lb.shrink < 1.0})
+        _refuse(_OPTIMIZE_REFUSES, _who(cost, gd, lbfgs), {what for what, yes in asked.items() if yes})
         if host and route != "ba_lists":   # the stepping form (toa_lm_begin / toa_jit_lm_begin, step, stop)
             return _optimize_with_host_controls(x, cost, options, history, ctx)
         # gd::Optimizer (optimizers/gd.h) on a scalar cost model: no final Hessian (optimizer.h:313)
         gd_run = gd and route == "jit" and cost.res.kind in JitResidual.COST_KINDS
+        lbfgs_run = lbfgs   # (whatever is no first-order cost model was refused above)
     if gd_run and not cost.ragged:   # (the uniform GD entry asks for its defaults before the loss is set, the ragged one after: the order each had)
         gdo = _gd_pod(ctx, options)
-    pod, out, res = _run_prologue(x, cost, options, history, ctx, out, zero_counters, gd_run)
+    pod, out, res = _run_prologue(x, cost, options, history, ctx, out, zero_counters, gd_run or lbfgs_run)
     if gd_run and cost.ragged:
         gdo = _gd_pod(ctx, options)
+    if lbfgs_run:
+        lbo = _lbfgs_pod(ctx, options)
     lib = ctx.lib
     if route == "builtin":   # (spelled out, not over _head: the single-problem solves pay for every tuple built here)
         if splits is None:   # the library decides (row-split for few, huge problems: P * 4 <= #CUs and m >= 512)
@@ -1362,7 +1421,7 @@ def Optimize(x: torch.Tensor, cost, options: Optional[Options] = None, *, histor
             check(lib.toa_lm_run_split(ctx.h, cost.model_id, _dtype_code(x.dtype), cost.n, cost.m, x.shape[0], cost.packed.data_ptr(), x.data_ptr(),
                                        C.byref(pod), C.byref(res), out.counters.data_ptr(), int(splits)))
         return out
-    if route == "jit" and not (gd_run or cost.ragged) and cost.bounds is None and cost.prior is None:
+    if route == "jit" and not (gd_run or lbfgs_run or cost.ragged) and cost.bounds is None and cost.prior is None:
         # the plain uniform run-time model, spelled out for the same reason (and the only one with a row-split form)
         if splits is None:
             check(lib.toa_jit_lm_run(ctx.h, cost.res._h, cost.items, x.shape[0], cost.packed.data_ptr(), x.data_ptr(),
@@ -1380,6 +1439,9 @@ def Optimize(x: torch.Tensor, cost, options: Optional[Options] = None, *, histor
         if gd_run:           # (a loss on a scalar cost is refused by the library)
             res.final_hessian = None
             check(getattr(lib, _JIT_ENTRIES["gd_run"][key])(*head, run[0], C.byref(gdo), *run[1:]))
+        elif lbfgs_run:      # (no final Hessian either)
+            res.final_hessian = None
+            check(getattr(lib, _JIT_ENTRIES["lbfgs_run"][key])(*head, run[0], C.byref(lbo), *run[1:]))
         else:
             check(getattr(lib, _JIT_ENTRIES["lm_run"][key])(*(head + extras + run)))
     else:   # the two BA families (no final Hessian: the library is told so)
@@ -1411,7 +1473,7 @@ class Optimizer:
                  ctx: Optional[Context] = None):
         self.options = options or Options()
         _check_call(x, cost)
-        _refuse(_OPTIMIZER_REFUSES, _who(cost), ("Optimizer",))
+        _refuse(_OPTIMIZER_REFUSES, _who(cost) | ({"lbfgs"} if self.options.solver_type == _LBFGS_SOLVER else set()), ("Optimizer",))
         self.x, self.cost = x, cost
         self.ctx = ctx or default_context(x.device.index)
         self.pod = self.options.to_pod()

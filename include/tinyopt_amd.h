@@ -564,6 +564,26 @@ int toa_model_compile(toa_handle h, int dtype, int num_params, int residuals_per
  * kinds).  Refused with TOA_E_UNSUPPORTED: solver_type 2 / toa_jit_gd_run (the reference throws for this signature too), a loss on
  * the handle, the *_prior, *_bounds and *_ragged entries, toa_jit_lm_run_split, toa_jit_lm_begin / step / stop, toa_jit_eval. */
 #define TOA_JIT_COST_HESS 4
+/* Rank-one second-order scalar cost — c_i = phi(u_i(x)) with a SCALAR inner function u_i: logistic and Poisson regression, any GLM, any
+ * likelihood of a scalar predictor — run by LM / GN on the matrix-core Gram of the row models (ggn_cost.hpp), so
+ * that Newton's method reaches 63 parameters.  The body sees x[j], h[k], p[k] on plain T as a TOA_JIT_COST_GRAD body does.  It assigns
+ * `c`, the item's cost term, and inside `if (want_grad) { ... }` three things: `gs`, a scalar, dc/du; `hs`, a scalar, the curvature
+ * weight phi''(u); and J[a] for EVERY a < n, the direction grad u — assigned, not added.  The item contributes g += gs J and
+ * H += w J J^T, where w = hs when hs > wmin, w = wmin when hs <= wmin, and a NaN hs stays NaN; wmin = 2^-60 in fp32, 2^-200 in fp64.
+ * The phi'(u) hess u term is dropped: the generalised Gauss-Newton Hessian, exact when u is linear in x.  A negative or zero
+ * curvature contributes its gradient and, up to wmin, nothing to H, which stays positive semi-definite: this is a Gauss-Newton door,
+ * NOT a door for indefinite Hessians — TOA_JIT_COST_HESS remains that.  Loops over a need COMPILE-TIME bounds: J is the lane's row
+ * in registers, and a row indexed by a loop that is not unrolled lands in scratch memory (toa_jit_model_stats: scratch_bytes).
+ * The problem's cost is sum_i c_i as ONE residual, inlier ratio 1.  solver_type 1 (GaussNewton), or damping_init = 0, is Newton's
+ * method; save_last returns the undamped H of the last Build.  A non-finite c, gs, hs or J ends the problem with TOA_STOP_NAN_OR_INF.
+ * Euclidean parameters, residuals_per_item = 1, diff = TOA_DIFF_DEFAULT, large_n = 0, 1 <= num_params <= 63 in fp32 and fp64 —
+ * anything else is refused by toa_model_compile_ex with TOA_E_UNSUPPORTED.
+ * Served: toa_jit_lm_run (solver_type 0 and 1, uniform batches, a handle without a loss; never the automatic row-split),
+ * toa_jit_accumulate (g, cost, nres = 1 and, where H_dev is not NULL, the full symmetric [P][n][n] sum), toa_jit_model_stats,
+ * toa_jit_check_gradient (g only, as for the cost kinds).  Refused with TOA_E_UNSUPPORTED: solver_type 2 and 3 / toa_jit_gd_run /
+ * toa_jit_lbfgs_run, a loss on the handle, the *_prior, *_bounds and *_ragged entries, toa_jit_lm_run_split, toa_jit_lm_begin / step /
+ * stop, toa_jit_eval.  toa_jit_spec is unchanged and no symbol is added: TOA_ABI_VERSION stays 7. */
+#define TOA_JIT_COST_GGN 5
 /* Numerical differentiation (the reference's diff/num_diff.h: NumEval, EstimateNumJac, CreateNumDiffFunc1 / 2 with
  * Method::{kForward, kCentral, kFastCentral}): spec.diff != 0 differentiates a TOA_JIT_RESIDUAL or TOA_JIT_COST body by finite
  * differences with step spec.diff_h instead of Jets, so the body is only ever instantiated on plain T (S = T) and need not be

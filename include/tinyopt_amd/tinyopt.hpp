@@ -366,13 +366,18 @@ class RaggedJitModel;
 // What a body's text is (JitResidual's `kind`): the library's TOA_JIT_* by name
 enum JitKind {
   kJitResidual = TOA_JIT_RESIDUAL, kJitAccumulate = TOA_JIT_ACCUMULATE, kJitCost = TOA_JIT_COST, kJitCostGrad = TOA_JIT_COST_GRAD,
-  kJitCostHess = TOA_JIT_COST_HESS
+  kJitCostHess = TOA_JIT_COST_HESS, kJitCostGgn = TOA_JIT_COST_GGN
 };
 namespace detail {
 // What a second-order scalar cost (TOA_JIT_COST_HESS) does not take, in one sentence each
 inline void refuse_cost_hess(const char* what) {
   throw std::invalid_argument(std::string("tinyopt_amd: a second-order scalar cost (TOA_JIT_COST_HESS) runs in the uniform one-launch form through Optimize "
                                           "(LM / GN), Accumulate and diff::CheckGradient only: ") + what);
+}
+// What a rank-one second-order scalar cost (TOA_JIT_COST_GGN) does not take, in one sentence each
+inline void refuse_cost_ggn(const char* what) {
+  throw std::invalid_argument(std::string("tinyopt_amd: a rank-one second-order scalar cost (TOA_JIT_COST_GGN) runs in the uniform one-launch form through "
+                                          "Optimize (LM / GN), Accumulate and diff::CheckGradient only: ") + what);
 }
 }  // namespace detail
 template <typename Scalar>
@@ -396,6 +401,14 @@ class JitResidual {
   //   double; loops over a, b need compile-time bounds (H is a register triangle; stats().scratch_bytes shows a spill).  GradientDescent (the
   //   reference throws for this signature too), with_loss, with_prior, with_bounds, bind_ragged, host controls, the stepping Optimizer and
   //   diff::Eval / CalculateJac are refused (std::invalid_argument).
+  // kind = TOA_JIT_COST_GGN (kJitCostGgn): a rank-one second-order scalar cost c_i = phi(u_i(x)) with a scalar inner function (logistic and Poisson
+  //   regression, any GLM) on the matrix-core Gram of the row models — the body assigns `c` and, inside `if (want_grad)`, `gs` = dc/du, `hs` = the
+  //   curvature weight and J[a] = (grad u)[a] for every a < n (assigned, not added); the item adds g += gs J and H += w J J^T, w = hs clamped from
+  //   below at wmin (2^-60 in float, 2^-200 in double; a NaN stays): the generalised Gauss-Newton Hessian, positive semi-definite — not a door
+  //   for indefinite Hessians (kJitCostHess remains that).  Run by LM / GN (GaussNewton, or lm.damping_init = 0: Newton's method).  Euclidean,
+  //   one cost term per item, 1 <= n <= 63 in float and double; loops over a need compile-time bounds (stats().scratch_bytes shows a spill).
+  //   GradientDescent, LBFGS, with_loss, with_prior, with_bounds, bind_ragged, host controls, the stepping Optimizer and diff::Eval /
+  //   CalculateJac are refused (std::invalid_argument).
   // large_n = true: the model is compiled for the launch-per-phase pipeline of the wide problems instead of a wavefront per problem —
   //   n up to 1024 (float) / 512 (double), item_scalars up to 2048; TOA_JIT_RESIDUAL / TOA_JIT_ACCUMULATE, Euclidean, TOA_DIFF_DEFAULT.
   //   Optimize (LM / GN), Accumulate and diff::Eval / CalculateJac take it; with_loss, with_prior, with_bounds, bind_ragged, splits, the stepping
@@ -425,6 +438,7 @@ class JitResidual {
   // host scalars, the items of all problems one after another; header: [P][header_scalars] (null without a header).
   RaggedJitModel<Scalar> bind_ragged(const std::vector<int64_t>& counts, const Scalar* data, const Scalar* header = nullptr) const {
     if (kind_ == TOA_JIT_COST_HESS) detail::refuse_cost_hess("no ragged batches (bind_ragged)");
+    if (kind_ == TOA_JIT_COST_GGN) detail::refuse_cost_ggn("no ragged batches (bind_ragged)");
     return RaggedJitModel<Scalar>(*this, counts, data, header);
   }
   const std::string& compile_log() const { return log_; }
@@ -479,6 +493,7 @@ class PriorTag {
  protected:
   void set_prior(const JitResidual<Scalar>& res, int64_t P, const Scalar* mu, const Scalar* W, int rows) {
     if (res.kind() == TOA_JIT_COST_HESS) detail::refuse_cost_hess("no Gaussian prior (with_prior): a prior is a block of residuals, and it has none");
+    if (res.kind() == TOA_JIT_COST_GGN) detail::refuse_cost_ggn("no Gaussian prior (with_prior): hand a ridge term over as extra items whose J is a unit vector");
     if (res.kind() == TOA_JIT_COST || res.kind() == TOA_JIT_COST_GRAD)
       throw std::invalid_argument("tinyopt_amd::with_prior: a scalar cost model has no residuals to add a Gaussian prior to");
     if (res.manifold() != TOA_MANIFOLD_EUCLID)
@@ -522,6 +537,7 @@ class BoundsTag {
     if (res.large_n())
       throw std::invalid_argument("tinyopt_amd::with_bounds: a model compiled with large_n takes no box bounds");
     if (res.kind() == TOA_JIT_COST_HESS) detail::refuse_cost_hess("no box bounds (with_bounds): they project the Gauss-Newton system of a residual model");
+    if (res.kind() == TOA_JIT_COST_GGN) detail::refuse_cost_ggn("no box bounds (with_bounds)");
     if (res.kind() == TOA_JIT_COST || res.kind() == TOA_JIT_COST_GRAD)
       throw std::invalid_argument("tinyopt_amd::with_bounds: a scalar cost model has no Gauss-Newton system to project");
     if (res.manifold() != TOA_MANIFOLD_EUCLID)
@@ -725,6 +741,12 @@ BatchOutput Optimize(std::vector<Scalar>& x, const Cost& cost, const Options& op
       if (gd) detail::refuse_cost_hess("no GradientDescent: the reference throws for f(x, grad, H) under GradientDescent too (optimize.h:59-75)");
       if (cost.loss_kind != TOA_LOSS_L2) detail::refuse_cost_hess("no M-estimator (with_loss): a scalar cost has no residuals to robustify");
       if (options.has_host_controls()) detail::refuse_cost_hess("no stepping form, so no host controls (stop callbacks, max_duration_ms, the log line)");
+    }
+    if (cost.kind() == TOA_JIT_COST_GGN) {
+      if (gd) detail::refuse_cost_ggn("no GradientDescent: run the same cost as kJitCostGrad");
+      if (lbfgs) detail::refuse_cost_ggn("no L-BFGS: run the same cost as kJitCostGrad");
+      if (cost.loss_kind != TOA_LOSS_L2) detail::refuse_cost_ggn("no M-estimator (with_loss): a scalar cost has no residuals to robustify");
+      if (options.has_host_controls()) detail::refuse_cost_ggn("no stepping form, so no host controls (stop callbacks, max_duration_ms, the log line)");
     }
   }
   if (detail::has_bounds(cost)) {

@@ -308,6 +308,8 @@ class _LossMixin(_Model):
             _refuse_large_n("no M-estimator (with_loss): the pipeline's loss is per row, an item's is on its squared norm")
         if loss not in (None, "l2") and _is_cost_hess(self):
             _refuse_cost_hess("no M-estimator (with_loss): a scalar cost has no residuals to robustify")
+        if loss not in (None, "l2") and _is_cost_ggn(self):
+            _refuse_cost_ggn("no M-estimator (with_loss): a scalar cost has no residuals to robustify")
         m = copy.copy(self)          # shares the device data
         m.loss, m.th = (loss if loss not in (None, "l2") else None), float(th)
         return m
@@ -366,6 +368,8 @@ class _PriorMixin(_Model):
             _refuse_large_n("no Gaussian prior (with_prior)")
         if _is_cost_hess(self):
             _refuse_cost_hess("no Gaussian prior (with_prior): a prior is a block of residuals, and it has none")
+        if _is_cost_ggn(self):
+            _refuse_cost_ggn("no Gaussian prior (with_prior): hand a ridge term over as extra items whose J is a unit vector")
         if res.kind in JitResidual.COST_KINDS:
             _refuse_prior('a scalar cost model (kind="cost" / "cost_grad", GradientDescent) has no residuals to add a prior to')
         if res.manifold != "euclid":
@@ -420,6 +424,8 @@ class _BoundsMixin(_Model):
             _refuse_large_n("no box bounds (with_bounds)")
         if _is_cost_hess(self):
             _refuse_cost_hess("no box bounds (with_bounds): they project the Gauss-Newton system of a residual model")
+        if _is_cost_ggn(self):
+            _refuse_cost_ggn("no box bounds (with_bounds)")
         if res.kind in JitResidual.COST_KINDS:
             _refuse_bounds('a scalar cost model (kind="cost" / "cost_grad", GradientDescent) has no Gauss-Newton system to project')
         if res.manifold != "euclid":
@@ -505,6 +511,15 @@ def _is_cost_hess(cost) -> bool:
     return cost.route == "jit" and getattr(cost.res, "kind", None) == "cost_hess"
 
 
+def _refuse_cost_ggn(what: str):
+    raise ValueError(f'a rank-one second-order scalar cost (kind="cost_ggn") runs in the uniform one-launch form through Optimize (LM / GN), '
+                     f"accumulate and CheckGradient only: {what}")
+
+
+def _is_cost_ggn(cost) -> bool:
+    return cost.route == "jit" and getattr(cost.res, "kind", None) == "cost_ggn"
+
+
 def _refuse_ragged(what: str):
     raise ValueError(f"a ragged batch (bind_ragged) runs in the one-launch form only: {what}")
 
@@ -559,9 +574,16 @@ _REFUSALS = {
     ("lbfgs_cost", "lbfgs.shrink"): "L-BFGS: lbfgs.shrink (the backtracking factor) must be in (0, 1)",
     ("lbfgs", "Optimizer"): "L-BFGS (Options.LBFGS) has no stepping form (Optimizer): run it through Optimize",
     **{("cost_hess", what): f"no {what} (it has no residual rows: accumulate returns its value, its gradient and its Hessian)" for what in ("Eval", "CalculateJac")},
+    # a rank-one second-order scalar cost (kind="cost_ggn"): LM / GN in the uniform one-launch form
+    ("cost_ggn", "gd"): _NO_GD + ': run the same cost as kind="cost_grad"',
+    ("cost_ggn", "lbfgs"): 'no L-BFGS: run the same cost as kind="cost_grad"',
+    ("cost_ggn", "splits"): _NO_SPLITS, ("cost_ggn", "host"): _NO_HOST, ("cost_ggn", "Optimizer"): _NO_STEPPING,
+    **{("cost_ggn", what): f"no {what} (it has no residual rows: accumulate returns its value, its gradient and its Hessian)" for what in ("Eval", "CalculateJac")},
 }
-_REFUSE_AS = {"ragged": _refuse_ragged, "bounds": _refuse_bounds, "prior": _refuse_prior, "large_n": _refuse_large_n, "cost_hess": _refuse_cost_hess}
-_OPTIMIZE_REFUSES = (("cost_hess", "lbfgs"), ("bounds", "lbfgs"), ("prior", "lbfgs"), ("large_n", "lbfgs"), ("not_cost", "lbfgs"),
+_REFUSE_AS = {"ragged": _refuse_ragged, "bounds": _refuse_bounds, "prior": _refuse_prior, "large_n": _refuse_large_n, "cost_hess": _refuse_cost_hess,
+              "cost_ggn": _refuse_cost_ggn}
+_OPTIMIZE_REFUSES = (("cost_ggn", "lbfgs"), ("cost_ggn", "gd"), ("cost_ggn", "splits"), ("cost_ggn", "host"),
+                     ("cost_hess", "lbfgs"), ("bounds", "lbfgs"), ("prior", "lbfgs"), ("large_n", "lbfgs"), ("not_cost", "lbfgs"),
                      ("lbfgs_cost", "host"), ("lbfgs_cost", "splits"), ("lbfgs_cost", "grad_clipping"), ("lbfgs_cost", "lbfgs.history"),
                      ("lbfgs_cost", "lbfgs.c1"), ("lbfgs_cost", "lbfgs.shrink"),
                      ("cost_hess", "gd"), ("cost_hess", "splits"), ("cost_hess", "host"), ("ragged", "splits"), ("ragged", "host"), ("uniform", "keep_order"), ("ba", "host"), ("ba", "splits"),
@@ -569,9 +591,9 @@ _OPTIMIZE_REFUSES = (("cost_hess", "lbfgs"), ("bounds", "lbfgs"), ("prior", "lbf
                      ("bounds", "splits"), ("bounds", "host"), ("bounds", "gd"), ("prior", "splits"), ("prior", "host"), ("prior", "gd"),
                      ("large_n", "splits"), ("large_n", "host"), ("large_n", "gd"), ("large_n", "capture"), ("numeric", "host"), ("numeric", "splits"),
                      ("gd_cost", "host"), ("gd_cost", "splits"), ("stepping", "out with host controls"))
-_OPTIMIZER_REFUSES = tuple((who, "Optimizer") for who in ("lbfgs", "cost_hess", "ragged", "bounds", "prior", "numeric", "large_n"))
+_OPTIMIZER_REFUSES = tuple((who, "Optimizer") for who in ("lbfgs", "cost_hess", "cost_ggn", "ragged", "bounds", "prior", "numeric", "large_n"))
 _CHECK_GRADIENT_REFUSES = tuple((who, "CheckGradient") for who in ("bounds", "prior", "ragged", "large_n"))
-_ROWS_REFUSES = {what: (("cost_hess", what), ("bounds", what), ("prior", what)) for what in ("Eval", "CalculateJac")}
+_ROWS_REFUSES = {what: (("cost_hess", what), ("cost_ggn", what), ("bounds", what), ("prior", what)) for what in ("Eval", "CalculateJac")}
 
 
 def _who(cost, gd: bool = False, lbfgs: bool = False) -> set:
@@ -592,6 +614,8 @@ def _who(cost, gd: bool = False, lbfgs: bool = False) -> set:
         who.add("lbfgs_cost" if cost.route == "jit" and cost.res.kind in JitResidual.COST_KINDS else "not_cost")
     if _is_cost_hess(cost):
         who.add("cost_hess")
+    if _is_cost_ggn(cost):
+        who.add("cost_ggn")
     if cost.route != "ba_lists":   # (it honours max_duration_ms itself; every other family goes to the stepping form for host controls)
         who.add("stepping")
     return who
@@ -862,6 +886,30 @@ class JitResidual:
             }''', n=12, item_scalars=13, kind="cost_hess", dtype=torch.float64)
         out = ta.Optimize(w, newton.bind(samples), ta.Options())        # samples: [P, items, 13] on the GPU
 
+    Rank-one second-order scalar costs — ``kind="cost_ggn"``: a cost ``c_i = phi(u_i(x))`` with a SCALAR inner function (logistic
+    and Poisson regression, any GLM, any likelihood of a scalar predictor), run by LM or GN on the matrix-core Gram of the row
+    models, so that Newton's method reaches 63 parameters.  The body sees ``x[j]``, ``h[k]``, ``p[k]`` on plain T; it assigns ``c``
+    and, inside ``if (want_grad) { ... }``, three things: ``gs`` = dc/du, ``hs`` = the curvature weight phi''(u), and ``J[a]`` =
+    (grad u)[a] for EVERY a < n (assigned, not added).  The item contributes ``g += gs J`` and ``H += w J J^T`` with ``w = hs``
+    where ``hs > wmin``, ``wmin`` where ``hs <= wmin`` (2^-60 in float32, 2^-200 in float64) and NaN where ``hs`` is NaN: the
+    generalised Gauss-Newton Hessian (the phi'(u) hess u term is dropped; exact where u is linear in x).  A negative or zero
+    curvature contributes its gradient and, up to wmin, nothing to H, which stays positive semi-definite: a Gauss-Newton door, not
+    one for indefinite Hessians (``cost_hess`` remains that).  The problem's cost is the sum of the items' ``c`` as ONE residual.
+    Loops over ``a`` need COMPILE-TIME bounds (``J`` is the lane's row in registers; ``stats()["scratch_bytes"]`` shows a
+    violation).  Euclidean parameters, one cost term per item, ``diff="ad"``, 1 <= n <= 63 in float32 and float64.  ``Optimize``
+    (LM / GN; ``Options.GaussNewton`` or ``lm.damping_init = 0`` is Newton's method), ``accumulate`` (g, the full symmetric H, cost)
+    and ``CheckGradient`` take such a model (``check_H=True`` agrees only where u is linear in x or phi' vanishes);
+    GradientDescent, L-BFGS, ``with_loss``, ``with_prior``, ``with_bounds``, ``bind_ragged``, ``splits``, the stepping ``Optimizer``,
+    host controls, ``Eval`` / ``CalculateJac``, manifolds, numeric ``diff`` and ``large_n`` are refused with a sentence.  Logistic
+    regression at n = 50 (an item = 50 features + the label +-1)::
+
+        newton50 = ta.JitResidual('''
+            T z = 0; for (int j = 0; j < 50; ++j) z += p[j] * x[j];
+            const T y = p[50], e = exp(-y * z), s = T(1) / (T(1) + e);
+            c = log(T(1) + e);
+            if (want_grad) { gs = -y * (T(1) - s); hs = s * (T(1) - s); for (int a = 0; a < 50; ++a) J[a] = p[a]; }''',
+            n=50, item_scalars=51, kind="cost_ggn", dtype=torch.float32)
+
     Numerical differentiation (the reference's diff/num_diff.h: ``NumEval`` / ``CreateNumDiffFunc1/2``) — ``diff="forward"``,
     ``"central"`` or ``"fast_central"`` with step ``diff_h`` (0 = FloatEpsilon: 1e-4 in float32, 1e-7 in float64) differentiates a
     ``kind="residual"`` or ``kind="cost"`` body by finite differences instead of Jets: the body is only ever instantiated on the
@@ -879,9 +927,10 @@ class JitResidual:
     solve.  Without ``large_n`` a model of 64 parameters is refused as before.  ``stats()`` then describes the rows kernel."""
 
     MANIFOLDS = {"euclid": 0, "se3": 1, "user": 2}
-    KINDS = {"residual": 0, "accumulate": 1, "cost": 2, "cost_grad": 3, "cost_hess": 4}
+    KINDS = {"residual": 0, "accumulate": 1, "cost": 2, "cost_grad": 3, "cost_hess": 4, "cost_ggn": 5}
     COST_KINDS = ("cost", "cost_grad")   # the first-order kinds (GradientDescent); "cost_hess" runs under LM / GN
     COST_HESS_MAX_N = 12
+    COST_GGN_MAX_N = 63
     DIFFS = {"ad": 0, "forward": 1, "central": 2, "fast_central": 3}
 
     def __init__(self, body: str, n: int, item_scalars: int, residuals_per_item: int = 1, header_scalars: int = 0,
@@ -913,6 +962,17 @@ class JitResidual:
             if not 1 <= self.n <= self.COST_HESS_MAX_N:
                 _refuse_cost_hess(f"1 <= n <= {self.COST_HESS_MAX_N} in float32 and float64 (the Hessian's triangle, n (n + 1) / 2 <= 78 accumulators, is "
                                   f"kept in registers), not n = {self.n} ({self.n * (self.n + 1) // 2} accumulators)")
+        if kind == "cost_ggn":   # (the library refuses the same, toa_model_compile_ex: here before anything is compiled)
+            if manifold != "euclid":
+                _refuse_cost_ggn(f"Euclidean parameters only, not manifold={manifold!r}")
+            if diff != "ad":
+                _refuse_cost_ggn(f'the body brings its own derivatives, nothing is differentiated: diff="ad" only, not diff={diff!r}')
+            if self.large_n:
+                _refuse_cost_ggn("no large_n (the launch-per-phase pipeline is for residual models)")
+            if self.kR != 1:
+                _refuse_cost_ggn(f"an item has one cost term: residuals_per_item = 1, not {self.kR}")
+            if not 1 <= self.n <= self.COST_GGN_MAX_N:
+                _refuse_cost_ggn(f"1 <= n <= {self.COST_GGN_MAX_N} in float32 and float64 (one wavefront per problem), not n = {self.n}")
         if self.large_n:   # (the library refuses the same, toa_model_compile_ex: here before anything is compiled)
             if kind in self.COST_KINDS:
                 _refuse_large_n('no scalar costs (kind="cost" / "cost_grad") and no GradientDescent')
@@ -970,6 +1030,8 @@ class JitResidual:
             _refuse_large_n("no ragged batches (bind_ragged)")
         if self.kind == "cost_hess":
             _refuse_cost_hess("no ragged batches (bind_ragged)")
+        if self.kind == "cost_ggn":
+            _refuse_cost_ggn("no ragged batches (bind_ragged)")
         return RaggedJitModel(self, data, counts, offsets, header)
 
     def stats_prior(self, ragged: bool = False) -> dict:
@@ -1683,7 +1745,8 @@ def CheckGradient(model: "JitModel", x: torch.Tensor, eps: Optional[float] = Non
     x [P, n]: the model's own derivatives against finite differences of its residuals (or cost terms) with step eps / 10.
     Residual kinds compare g = J^T r and, with ``check_H``, H = J^T J; cost kinds compare g; ``kind="cost_hess"`` compares g and, with
     ``check_H``, the body's H with central differences of the body's own gradient (2 n ``accumulate`` calls on shifted copies of x,
-    step eps / 10), returned as ``max_dist_H``.  ``eps`` None: the reference's default
+    step eps / 10), returned as ``max_dist_H``; ``kind="cost_ggn"`` does the same with its H = sum w J J^T, which agrees with those
+    differences only where u is linear in x or phi' vanishes (the phi'(u) hess u term is dropped).  ``eps`` None: the reference's default
     (1e-2 in float32, 1e-5 in float64).  The first check of a model with a (method, eps) compiles its numeric twin (then cached)."""
     if not isinstance(model, _JitBatch):
         raise TypeError("CheckGradient takes a bound run-time model (JitResidual.bind)")
@@ -1701,7 +1764,7 @@ def CheckGradient(model: "JitModel", x: torch.Tensor, eps: Optional[float] = Non
                                          JitResidual.DIFFS[method], int(bool(check_H)), dist.data_ptr(), ok.data_ptr()))
     if eps is None:
         e = 1e-2 if x.dtype == torch.float32 else 1e-5
-    if check_H and _is_cost_hess(model):
+    if check_H and (_is_cost_hess(model) or _is_cost_ggn(model)):
         # The body's H against central differences of the body's OWN gradient with the checker's step eps / 10 (gradient_check.h:96,201):
         # 2 n Accumulate calls on shifted copies of x, no device code of its own.  Column a of the numeric H is (g(x + h e_a) - g(x - h e_a)) / (2 h).
         n, step = model.n, e / 10.0

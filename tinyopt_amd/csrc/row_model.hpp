@@ -233,6 +233,15 @@ template <typename F, typename = void>
 struct FunctorTable { static constexpr int bytes = 0; };
 template <typename F>
 struct FunctorTable<F, std::enable_if_t<F::kTable>> { static constexpr int bytes = F::kTableBytes; };
+// Extension point (ggn_cost.hpp): a functor with kItemCost supplies every item's COST TERM itself, beside its row —
+//   template <bool want_grad> eval_item(x, h, p, T& c, T* r, T (*J)[kN])
+// The pass then sums c per lane and returns the wave's sum on both passes: the problem's cost is that sum as ONE residual, the
+// Gram's (r, r) entry and the rows' squared norms are not read, and the model keeps no memo (its cost is no Gram entry).  No
+// functor without the flag sees any of it: every use is behind `if constexpr`.
+template <typename F, typename = void>
+struct FunctorItemCost { static constexpr bool value = false; };
+template <typename F>
+struct FunctorItemCost<F, std::enable_if_t<F::kItemCost>> { static constexpr bool value = true; };
 
 // MANIFOLD: 0 = Euclidean, 1 = ONE SE3 pose (12 stored scalars, six tangent dimensions), 2 = the user's container (TOA_MANIFOLD_USER:
 // F::kX stored scalars, F::plus; round 6).  A functor with
@@ -246,6 +255,8 @@ struct RowModel {
   static constexpr int kXdim = MANIFOLD == 1 ? 12 : (MANIFOLD == 2 ? FunctorX<F>::value : 0);
   static_assert(kXdim <= 64, "stored scalars of x: one per lane");
   static constexpr int kTableBytes = FunctorTable<F>::bytes;
+  static constexpr bool kItemCost = FunctorItemCost<F>::value;
+  static_assert(!kItemCost || (!ROBUST && MANIFOLD == 0 && kTableBytes == 0 && F::kR == 1), "an item-cost functor: plain Euclidean rows, one per item");
   static constexpr int kN = F::kN, kR = F::kR, kD = F::kD;
   static constexpr int kNmax = THIN > 0 ? 16 * NBM + THIN - 1 : 16 * NBM - 1;
   static constexpr int kNpad = (kNmax + 7) & ~7;
@@ -494,7 +505,12 @@ struct RowModel {
           }
         }
 #else
-        if constexpr (kTableBytes > 0) {
+        if constexpr (kItemCost) {
+          T ci = T(0);
+          if constexpr (WANT_H) F::template eval_item<true>(xp, d, p, ci, rv, Jv);
+          else F::template eval_item<false>(xp, d, p, ci, rv, static_cast<T(*)[kN]>(nullptr));
+          csum += ci;
+        } else if constexpr (kTableBytes > 0) {
           if constexpr (WANT_H) F::template eval_manual_tab<true>(xp, reinterpret_cast<const typename F::TabJet*>(stg + kGeom.table_off), d, p, rv, Jv);
           else F::template eval_manual_tab<false>(xp, nullptr, d, p, rv, static_cast<T(*)[kN]>(nullptr));
         } else {
@@ -512,7 +528,7 @@ struct RowModel {
         csum += valid ? l : T(0);
         inl += (valid && n2 <= th2) ? T(kR) : T(0);
         sq = r_sqrt(sc);
-      } else if constexpr (!WANT_H) {
+      } else if constexpr (!WANT_H && !kItemCost) {
         csum += n2;
       }
       if constexpr (!WANT_H) wave_sync();   // (the region is overwritten two super-steps on: not before every lane has read its item)
@@ -595,7 +611,8 @@ struct RowModel {
     ninl = robust ? int(wave_allreduce_sum(inl)) : -1;   // exact in T: one count per residual
     if constexpr (WANT_H) {
       gram.finish_steps();
-      return robust ? wave_allreduce_sum(csum) : T(0);
+      if constexpr (kItemCost) return wave_allreduce_sum(csum);
+      else return robust ? wave_allreduce_sum(csum) : T(0);
     }
     return wave_allreduce_sum(csum);
   }
@@ -606,16 +623,18 @@ struct RowModel {
     else cl = pass<true, kGeom.items2, kGeom.nbuf>(L.xs, lane);
     cost = gram.extract_g_diag_cost(L.g, L.hd, lay, n, lane, L.tmp);
     if (ROBUST && loss != TOA_LOSS_L2) cost = cl;   // sum of the robust losses, not the Gram's r^T r (which is scaled by s)
-    nres = m;
+    if constexpr (kItemCost) { cost = cl; nres = 1; }   // the items' own cost terms, ONE residual
+    else nres = m;
   }
   __device__ __forceinline__ void evaluate(WaveLds<T>& L, int, int lane, T& cost, int& nres) {
     cost = pass<false, kGeom.items2, kGeom.nbuf>(L.xs, lane);
-    nres = m;
+    if constexpr (kItemCost) nres = 1;
+    else nres = m;
   }
   template <typename O>
   __device__ __forceinline__ void write_sym(O* M, int LD, int n, int lane) const { gram.write_sym(M, LD, lay, n, lane); }
   // memo of the last accepted linearisation (lm_device.hpp)
-  static constexpr bool kMemo = true;
+  static constexpr bool kMemo = !kItemCost;
   static constexpr size_t kMemoBytes = size_t(DenseRowGram<T, NBM, THIN>::kMemoElems) * sizeof(T);
   __device__ __forceinline__ void memo_save(WaveLds<T>& L, int lane) const { gram.memo_save(reinterpret_cast<T*>(L.st->memo_slot), lane); }
   __device__ __forceinline__ void memo_reextract(WaveLds<T>& L, int n, int lane, T& cost, int& nres) {

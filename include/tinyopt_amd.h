@@ -618,7 +618,16 @@ typedef struct toa_jit_spec {
                          TOA_JIT_RESIDUAL / TOA_JIT_ACCUMULATE, Euclidean parameters, diff = TOA_DIFF_DEFAULT, 1 <= num_params <= 1024 in
                          fp32 / 512 in fp64, scalars_per_item <= 2048.  Such a model is taken by toa_jit_lm_run (LM / GN, no M-estimator, not
                          under stream capture), toa_jit_accumulate and toa_jit_eval; every other toa_jit_* entry refuses it with
-                         TOA_E_UNSUPPORTED.  toa_jit_model_stats describes its rows kernel.  reserved[1..3] stay zero. */
+                         TOA_E_UNSUPPORTED.  toa_jit_model_stats describes its rows kernel.  reserved[2..3] stay zero. */
+    struct {
+      int32_t toa_pad0_;        /* NOT a field: the word large_n names (reserved[0]); it only places shared_scalars on reserved[1].  Write large_n.
+                                   (An unnamed struct in an unnamed union: C11, and an extension every C++ compiler this library builds with
+                                   accepts — g++ / clang++ warn under -Wpedantic only.) */
+      int32_t shared_scalars;   /* = reserved[1].  0 = as before.  1 .. 512: the body sees one more array, s[k] for 0 <= k < shared_scalars —
+                                   for item i of EVERY problem row i of one table [items][shared_scalars] handed over per call (toa_shared
+                                   below).  TOA_JIT_RESIDUAL (Jets or diff = TOA_DIFF_NUM_*), TOA_JIT_ACCUMULATE and TOA_JIT_COST_GGN, Euclidean
+                                   parameters, large_n = 0; scalars_per_item = 0 is legal beside it. */
+    };
   };
 } toa_jit_spec;
 int toa_model_compile_ex(toa_handle h, const toa_jit_spec* spec, const char* body, toa_jit_model* out, char* log_out, size_t log_cap);
@@ -830,6 +839,29 @@ int toa_jit_accumulate_ragged_bounds(toa_handle h, toa_jit_model model, const in
                                      int64_t total_items, int64_t P, const void* data_dev, const void* x_dev, const toa_bounds* bounds,
                                      const toa_prior* prior, int want_grad, void* g_dev, void* H_dev, double* cost_dev, int32_t* nres_dev);
 int toa_jit_model_stats_bounds(toa_handle h, toa_jit_model m, int ragged, int with_prior, int* wg_per_cu, int* num_regs, int* scratch_bytes);
+/*      Shared item tables: ONE table of item data for a whole batch.  A model compiled with
+ *      toa_jit_spec::shared_scalars = kS > 0 reads, for item i of every problem, row i of table_dev [rows][kS] (the model's scalar
+ *      type) as s[0 .. kS) beside the item's private scalars p[0 .. scalars_per_item) and the problem's header h: one design matrix
+ *      for a GLM per gene, one time axis for a curve fit per pixel, one map for many poses.  data_dev stays
+ *      [P][header_scalars + num_items * scalars_per_item]; the caller replicates nothing.  The rows are staged into LDS beside the
+ *      private items by the same LDS-DMA, so HBM streams the private part only; the table is expected to be served by the L2 after its first reader (not measured with counters).
+ *      Such a model is a row model at every 1 <= num_params <= 63 and 1 <= residuals_per_item <= 8, and runs through the two entries
+ *      below only: they mirror toa_jit_lm_run_bounds / toa_jit_accumulate_bounds (same checks in the same order, same results; bounds
+ *      and prior may each be NULL) with the table after data_dev.  toa_set_loss applies to the residual kinds; TOA_JIT_COST_GGN keeps
+ *      refusing a loss, a prior and bounds.  Always the one-launch form, never the row-split.
+ *      TOA_E_ARG: a NULL shared / table_dev, rows != num_items, rows * kS * sizeof(scalar) >= 4 GiB (one buffer descriptor), a table on
+ *      another device.  TOA_E_UNSUPPORTED: a model without shared scalars at these two entries; a model WITH them at every other
+ *      toa_jit_* run, accumulate, eval, stepping, row-split, gradient-descent, L-BFGS, ragged and check-gradient entry; at compile time
+ *      shared_scalars > 0 with TOA_JIT_COST / TOA_JIT_COST_GRAD / TOA_JIT_COST_HESS, a manifold or large_n (shared_scalars outside
+ *      0 .. 512: TOA_E_ARG).  toa_jit_model_stats and its _prior / _bounds forms describe the builds as for any model.
+ *      No symbol is removed and no POD changes size: TOA_ABI_VERSION stays 7. */
+typedef struct toa_shared { const void* table_dev; int64_t rows; int32_t reserved[4]; } toa_shared;   /* [rows][shared_scalars] */
+int toa_jit_lm_run_shared(toa_handle h, toa_jit_model model, int num_items, int64_t P, const void* data_dev, const toa_shared* shared,
+                          void* x_dev, const toa_bounds* bounds /* may be NULL */, const toa_prior* prior /* may be NULL */,
+                          const toa_options* options, const toa_results* results, uint64_t* counters_dev);
+int toa_jit_accumulate_shared(toa_handle h, toa_jit_model model, int num_items, int64_t P, const void* data_dev, const toa_shared* shared,
+                              const void* x_dev, const toa_bounds* bounds, const toa_prior* prior, int want_grad, void* g_dev, void* H_dev,
+                              double* cost_dev, int32_t* nres_dev);
 
 /* ---- C1: the result gather of a sharded batch (SURVEY §8(b) export list `gather(handle_group...)`, §8(e)).
  *      Problems are independent (the reference optimises exactly one x per call, docs/API.md:12), so a batch of P_total

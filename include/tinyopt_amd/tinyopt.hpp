@@ -379,6 +379,11 @@ inline void refuse_cost_ggn(const char* what) {
   throw std::invalid_argument(std::string("tinyopt_amd: a rank-one second-order scalar cost (TOA_JIT_COST_GGN) runs in the uniform one-launch form through "
                                           "Optimize (LM / GN), Accumulate and diff::CheckGradient only: ") + what);
 }
+// What a model with a shared item table (JitResidual's shared_scalars > 0) does not take, in one sentence each
+inline void refuse_shared(const char* what) {
+  throw std::invalid_argument(std::string("tinyopt_amd: a model with a shared item table (shared_scalars > 0) runs in the uniform one-launch form through "
+                                          "Optimize (LM / GN) and Accumulate only: ") + what);
+}
 }  // namespace detail
 template <typename Scalar>
 class JitResidual {
@@ -413,11 +418,25 @@ class JitResidual {
   //   n up to 1024 (float) / 512 (double), item_scalars up to 2048; TOA_JIT_RESIDUAL / TOA_JIT_ACCUMULATE, Euclidean, TOA_DIFF_DEFAULT.
   //   Optimize (LM / GN), Accumulate and diff::Eval / CalculateJac take it; with_loss, with_prior, with_bounds, bind_ragged, splits, the stepping
   //   Optimizer, host controls, GradientDescent and diff::CheckGradient are refused (std::invalid_argument).  Without it n = 64 is refused.
+  // shared_scalars = kS > 0: the body sees one more array, s[k] for 0 <= k < kS — for item i of EVERY problem row i of ONE
+  //   table [items][kS] handed over by bind_shared (one design matrix for a GLM per gene, one time axis for a curve fit per pixel); p[k] stays the
+  //   item's own scalars (item_scalars = 0 is legal beside it).  TOA_JIT_RESIDUAL (Jets or TOA_DIFF_NUM_*), TOA_JIT_ACCUMULATE and
+  //   TOA_JIT_COST_GGN, Euclidean, not large_n.  Optimize (LM / GN) and Accumulate take it, with_loss / with_prior / with_bounds as the kind
+  //   allows; bind, bind_ragged, GradientDescent, LBFGS, host controls, the stepping Optimizer, diff::Eval / CalculateJac and
+  //   diff::CheckGradient are refused (std::invalid_argument).
   JitResidual(const Context& ctx, const std::string& body, int n, int item_scalars, int residuals_per_item = 1, int header_scalars = 0,
               int manifold = TOA_MANIFOLD_EUCLID, int kind = TOA_JIT_RESIDUAL, const std::string& plus_body = std::string(), int x_scalars = 0,
-              int diff = TOA_DIFF_DEFAULT, float diff_h = 0.f, bool large_n = false)
+              int diff = TOA_DIFF_DEFAULT, float diff_h = 0.f, bool large_n = false, int shared_scalars = 0)
       : ctx_(&ctx), n_(n), kR_(residuals_per_item), kD_(item_scalars), kH_(header_scalars),
-        xdim_(manifold == TOA_MANIFOLD_SE3 ? 12 : (manifold == TOA_MANIFOLD_USER ? x_scalars : n)), diff_(diff), manifold_(manifold), kind_(kind), large_n_(large_n) {
+        xdim_(manifold == TOA_MANIFOLD_SE3 ? 12 : (manifold == TOA_MANIFOLD_USER ? x_scalars : n)), diff_(diff), manifold_(manifold), kind_(kind), large_n_(large_n),
+        kS_(shared_scalars) {
+    if (shared_scalars != 0) {   // (the library refuses the same, toa_model_compile_ex: here before anything is compiled)
+      if (shared_scalars < 0 || shared_scalars > 512) throw std::invalid_argument("tinyopt_amd::JitResidual: shared_scalars must be in 0 .. 512 (0 = no shared item table)");
+      if (kind == TOA_JIT_COST || kind == TOA_JIT_COST_GRAD || kind == TOA_JIT_COST_HESS)
+        detail::refuse_shared("kJitResidual, kJitAccumulate and kJitCostGgn take a table (the row models stage it)");
+      if (manifold != TOA_MANIFOLD_EUCLID) detail::refuse_shared("Euclidean parameters only");
+      if (large_n) detail::refuse_shared("no large_n");
+    }
     std::vector<char> log(1 << 16);
     toa_jit_spec spec{};
     spec.dtype = dtype_of<Scalar>(); spec.num_params = n; spec.residuals_per_item = residuals_per_item;
@@ -425,6 +444,7 @@ class JitResidual {
     if (manifold == TOA_MANIFOLD_USER) { spec.x_scalars = x_scalars; spec.plus_body = plus_body.c_str(); }
     spec.diff = diff; spec.diff_h = diff_h;
     spec.large_n = large_n ? 1 : 0;
+    spec.shared_scalars = shared_scalars;
     const int rc = toa_model_compile_ex(ctx.get(), &spec, body.c_str(), &h_, log.data(), log.size());
     log_ = log.data();
     check(rc);
@@ -433,12 +453,23 @@ class JitResidual {
   JitResidual(const JitResidual&) = delete;
   JitResidual& operator=(const JitResidual&) = delete;
   // data: [P][header_scalars + items * item_scalars] host scalars
-  JitModel<Scalar> bind(int64_t P, int items, const Scalar* data) const { return JitModel<Scalar>(*this, P, items, data); }
+  JitModel<Scalar> bind(int64_t P, int items, const Scalar* data) const {
+    if (kS_ > 0) detail::refuse_shared("bind has no table: bind_shared(P, items, data, table)");
+    return JitModel<Scalar>(*this, P, items, data);
+  }
+  // ... of a model with shared_scalars: table = [items][shared_scalars] host scalars, ONE for the whole batch (row i beside item i's own
+  // scalars, in every problem); data as for bind (null where header_scalars = item_scalars = 0)
+  JitModel<Scalar> bind_shared(int64_t P, int items, const Scalar* data, const Scalar* table) const {
+    if (kS_ == 0) throw std::invalid_argument("tinyopt_amd::bind_shared: the model has no shared item table (shared_scalars = 0): bind(P, items, data)");
+    if (!table) throw std::invalid_argument("tinyopt_amd::bind_shared: table must not be null");
+    return JitModel<Scalar>(*this, P, items, data, table);
+  }
   // A RAGGED batch: counts[p] items for problem p (0 is legal: that problem ends with kSkipped); data: [sum of counts][item_scalars]
   // host scalars, the items of all problems one after another; header: [P][header_scalars] (null without a header).
   RaggedJitModel<Scalar> bind_ragged(const std::vector<int64_t>& counts, const Scalar* data, const Scalar* header = nullptr) const {
     if (kind_ == TOA_JIT_COST_HESS) detail::refuse_cost_hess("no ragged batches (bind_ragged)");
     if (kind_ == TOA_JIT_COST_GGN) detail::refuse_cost_ggn("no ragged batches (bind_ragged)");
+    if (kS_ > 0) detail::refuse_shared("no ragged batches (bind_ragged)");
     return RaggedJitModel<Scalar>(*this, counts, data, header);
   }
   const std::string& compile_log() const { return log_; }
@@ -453,6 +484,7 @@ class JitResidual {
   int manifold() const { return manifold_; }   // TOA_MANIFOLD_*
   int kind() const { return kind_; }           // TOA_JIT_*
   bool large_n() const { return large_n_; }    // compiled for the launch-per-phase pipeline (up to 1024 / 512 parameters)
+  int shared_scalars() const { return kS_; }   // columns of the batch's shared item table, 0 = none
   // stats of the fused kernel with a Gaussian prior (with_prior), uniform or ragged: toa_jit_model_stats_prior
   struct PriorBuildStats { int wg_per_cu = 0, num_regs = 0, scratch_bytes = 0; };
   PriorBuildStats stats_prior(bool ragged = false) const {
@@ -474,6 +506,7 @@ class JitResidual {
   toa_jit_model h_ = nullptr;
   int n_, kR_, kD_, kH_, xdim_, diff_, manifold_, kind_;
   bool large_n_;
+  int kS_;
   std::string log_;
 };
 // A Gaussian prior beside a bound run-time model's items (toa_jit_*_prior): per problem r = W (x - mu) after the item pass —
@@ -573,6 +606,21 @@ class JitModel : public LossTag, public PriorTag<Scalar>, public BoundsTag<Scala
       : res_(&res), P_(P), items_(items), data_(res.ctx(), size_t(P) * (res.header_scalars() + size_t(items) * res.item_scalars())) {
     data_.upload(host);
   }
+  // ... with the batch's shared item table (JitResidual::bind_shared)
+  JitModel(const JitResidual<Scalar>& res, int64_t P, int items, const Scalar* host, const Scalar* table)
+      : res_(&res), P_(P), items_(items),
+        data_(res.ctx(), std::max<size_t>(1, size_t(P) * (res.header_scalars() + size_t(items) * res.item_scalars()))),   // (never a null data pointer)
+        table_(res.ctx(), std::max<size_t>(1, size_t(items) * size_t(res.shared_scalars()))) {
+    if (size_t(P) * (res.header_scalars() + size_t(items) * res.item_scalars()) > 0) data_.upload(host);
+    if (items > 0) table_.upload(table);
+    has_shared_ = true;
+  }
+  bool has_shared() const { return has_shared_; }
+  toa_shared shared_pod() const {
+    toa_shared s{};
+    s.table_dev = table_.data(); s.rows = items_;
+    return s;
+  }
   static constexpr int model_id = -1;
   int64_t P() const { return P_; }
   int n() const { return res_->n(); }
@@ -589,7 +637,8 @@ class JitModel : public LossTag, public PriorTag<Scalar>, public BoundsTag<Scala
   const JitResidual<Scalar>* res_;
   int64_t P_;
   int items_;
-  DeviceBuffer<Scalar> data_;
+  DeviceBuffer<Scalar> data_, table_;
+  bool has_shared_ = false;
 };
 // A JitResidual bound to a ragged batch (toa_jit_*_ragged): taken by Optimize (LM, GN; GradientDescent for cost kinds), diff::Eval
 // and diff::CalculateJac, whose outputs are concatenated like the items.  One-launch form only: no host controls (stop callbacks,
@@ -734,6 +783,11 @@ BatchOutput Optimize(std::vector<Scalar>& x, const Cost& cost, const Options& op
       throw std::invalid_argument("tinyopt_amd::Optimize: L-BFGS (Options::LBFGS) needs a scalar cost model (a JitResidual of a cost kind)");
   }
   if constexpr (detail::is_jit<Cost>::value) {
+    if (cost.has_shared()) {
+      if (lbfgs) detail::refuse_shared("no L-BFGS");
+      if (gd) detail::refuse_shared("no GradientDescent");
+      if (options.has_host_controls()) detail::refuse_shared("no stepping form, so no host controls (stop callbacks, max_duration_ms, the log line)");
+    }
     if (cost.diff() != TOA_DIFF_DEFAULT && options.has_host_controls())
       throw std::invalid_argument("tinyopt_amd::Optimize: a numerically differentiated model runs as one launch per solve: stop callbacks, "
                                   "max_duration_ms and the log line are not supported (it has no stepping form)");
@@ -816,7 +870,13 @@ BatchOutput Optimize(std::vector<Scalar>& x, const Cost& cost, const Options& op
                                   cost.data(), dx.data(), &pod, &r, nullptr, flags));
     }
   } else if constexpr (detail::is_jit<Cost>::value) {
-    if (gd) {   // gd::Optimizer on a scalar cost model (the library refuses any other model: optimize.h:59-75)
+    if (cost.has_shared()) {   // (GradientDescent and L-BFGS were refused above) the table beside the batch; bounds and prior, each or NULL
+      const toa_shared sh = cost.shared_pod();
+      const toa_bounds bd = cost.has_bounds() ? cost.bounds_pod() : toa_bounds{};
+      const toa_prior pr = cost.has_prior() ? cost.prior_pod() : toa_prior{};
+      check(toa_jit_lm_run_shared(ctx.get(), cost.jit_handle(), cost.items(), P, cost.data(), &sh, dx.data(), cost.has_bounds() ? &bd : nullptr,
+                                  cost.has_prior() ? &pr : nullptr, &pod, &r, nullptr));
+    } else if (gd) {   // gd::Optimizer on a scalar cost model (the library refuses any other model: optimize.h:59-75)
       const toa_gd_options gpod = options.gd_pod();
       check(toa_jit_gd_run(ctx.get(), cost.jit_handle(), cost.items(), P, cost.data(), dx.data(), &pod, &gpod, &r, nullptr));
     } else if (lbfgs) {   // (the library refuses any model that is no first-order scalar cost)
@@ -862,6 +922,8 @@ GradientCheck CheckGradient(const JitModel<Scalar>& model, const std::vector<Sca
   const int64_t P = model.P();
   if (int64_t(x.size()) != P * model.xdim())
     throw std::invalid_argument("tinyopt_amd::diff::CheckGradient: x must hold P * (parameters per problem) scalars");
+  if (model.has_shared())
+    detail::refuse_shared("no CheckGradient (compare Accumulate of a kJitAccumulate body with Accumulate of its residuals under diff::kCentral, both with the table)");
   if (model.has_bounds()) detail::refuse_bounds("no CheckGradient (it checks the model's own rows)");
   if (model.has_prior()) detail::refuse_prior("no CheckGradient (it checks the model's own rows)");
   const Context& ctx = model.ctx();
@@ -897,6 +959,7 @@ std::pair<std::vector<Scalar>, std::vector<Scalar>> Eval(const JitModel<Scalar>&
   const int64_t P = model.P();
   if (int64_t(x.size()) != P * model.xdim())
     throw std::invalid_argument("tinyopt_amd::diff::Eval: x must hold P * (parameters per problem) scalars");
+  if (model.has_shared()) detail::refuse_shared("no Eval / CalculateJac (their kernels read replicated items)");
   if (model.has_bounds()) detail::refuse_bounds("no Eval / CalculateJac (they return the model's own rows)");
   if (model.has_prior()) detail::refuse_prior("no Eval / CalculateJac (they return the model's own rows)");
   const Context& ctx = model.ctx();
@@ -919,6 +982,7 @@ std::vector<Scalar> CalculateJac(const JitModel<Scalar>& model, const std::vecto
   const int64_t P = model.P();
   if (int64_t(x.size()) != P * model.xdim())
     throw std::invalid_argument("tinyopt_amd::diff::CalculateJac: x must hold P * (parameters per problem) scalars");
+  if (model.has_shared()) detail::refuse_shared("no Eval / CalculateJac (their kernels read replicated items)");
   if (model.has_bounds()) detail::refuse_bounds("no Eval / CalculateJac (they return the model's own rows)");
   if (model.has_prior()) detail::refuse_prior("no Eval / CalculateJac (they return the model's own rows)");
   const Context& ctx = model.ctx();
@@ -977,6 +1041,9 @@ class Optimizer {
         state_(cost.ctx(), toa_lm_state_bytes(dtype_of<Scalar>(), n_, P_)) {
     if (int64_t(x.size()) != P_ * cost.xdim())
       throw std::invalid_argument("tinyopt_amd::Optimizer: x must hold P * (parameters per problem) scalars");
+    if constexpr (detail::is_jit<Cost>::value) {
+      if (cost.has_shared()) detail::refuse_shared("no stepping form (Optimizer)");
+    }
     if (detail::has_bounds(cost)) detail::refuse_bounds("no stepping form (Optimizer)");
     if (detail::has_prior(cost)) detail::refuse_prior("no stepping form (Optimizer)");
     dx_.upload(x.data());
@@ -1354,8 +1421,21 @@ void Accumulate(const Cost& cost, const std::vector<Scalar>& x, std::vector<Scal
   DeviceBuffer<Scalar> dg, dH;
   if (want) { dg = DeviceBuffer<Scalar>(ctx, size_t(P) * n); dH = DeviceBuffer<Scalar>(ctx, size_t(P) * n * n); }
   apply_loss(cost);
-  check(toa_accumulate(ctx.get(), Cost::model_id, dtype_of<Scalar>(), n, cost.m(), P, cost.data(), dx.data(), want ? 1 : 0,
-                       want ? dg.data() : nullptr, want ? dH.data() : nullptr, dc.data(), nullptr));
+  bool done = false;
+  if constexpr (detail::is_jit<Cost>::value) {
+    if (cost.has_shared()) {   // a model with a shared item table: the table beside the batch; bounds and prior, each or NULL
+      const toa_shared sh = cost.shared_pod();
+      const toa_bounds bd = cost.has_bounds() ? cost.bounds_pod() : toa_bounds{};
+      const toa_prior pr = cost.has_prior() ? cost.prior_pod() : toa_prior{};
+      check(toa_jit_accumulate_shared(ctx.get(), cost.jit_handle(), cost.items(), P, cost.data(), &sh, dx.data(), cost.has_bounds() ? &bd : nullptr,
+                                      cost.has_prior() ? &pr : nullptr, want ? 1 : 0, want ? dg.data() : nullptr, want ? dH.data() : nullptr, dc.data(),
+                                      nullptr));
+      done = true;
+    }
+  }
+  if (!done)
+    check(toa_accumulate(ctx.get(), Cost::model_id, dtype_of<Scalar>(), n, cost.m(), P, cost.data(), dx.data(), want ? 1 : 0,
+                         want ? dg.data() : nullptr, want ? dH.data() : nullptr, dc.data(), nullptr));
   check(toa_synchronize(ctx.get()));
   cost_out.resize(P);
   dc.download(cost_out.data());

@@ -68,8 +68,13 @@ class ToaTuning(C.Structure):   # include/tinyopt_amd.h toa_tuning
                                          "large_library_gram", "large_library_solver", "fail_workspace_alloc", "large_one_lane", "large_chol_no_lookahead", "large_gram_plain_deal", "narrow_mfma_pass", "se3_reproj_header_l2")] + [("reserved", C.c_int32 * 13)]
 
 
+class _ToaJitSpecTailWords(C.Structure):   # ... as named words: shared_scalars is reserved[1]
+    _fields_ = [("_pad0", C.c_int32), ("shared_scalars", C.c_int32)]
+
+
 class _ToaJitSpecTail(C.Union):   # toa_jit_spec's last four words: large_n is reserved[0]
-    _fields_ = [("reserved", C.c_int32 * 4), ("large_n", C.c_int32)]
+    _anonymous_ = ("_words",)
+    _fields_ = [("reserved", C.c_int32 * 4), ("large_n", C.c_int32), ("_words", _ToaJitSpecTailWords)]
 
 
 class ToaJitSpec(C.Structure):   # include/tinyopt_amd.h toa_jit_spec
@@ -93,6 +98,10 @@ class ToaPrior(C.Structure):   # include/tinyopt_amd.h toa_prior (rows = 0: the 
 
 class ToaBounds(C.Structure):   # include/tinyopt_amd.h toa_bounds (-inf / +inf: no bound; lo == hi: fixed)
     _fields_ = [("lo_dev", C.c_void_p), ("hi_dev", C.c_void_p), ("reserved", C.c_int32 * 4)]
+
+
+class ToaShared(C.Structure):   # include/tinyopt_amd.h toa_shared (one table [rows][shared_scalars] for every problem of a batch)
+    _fields_ = [("table_dev", C.c_void_p), ("rows", C.c_int64), ("reserved", C.c_int32 * 4)]
 
 
 class ToaBaConstant(C.Structure):   # include/tinyopt_amd.h toa_ba_constant (byte flags [P][C] / [P][N], non-zero: held constant; NULL: none)
@@ -181,6 +190,10 @@ PROTOTYPES = {
     "toa_jit_accumulate_ragged_bounds": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int64, C.c_int64, _P, _P, C.POINTER(ToaBounds), C.POINTER(ToaPrior),
                                                    C.c_int, _P, _P, _P, _P]),
     "toa_jit_model_stats_bounds": (C.c_int, [_P, _P, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "toa_jit_lm_run_shared": (C.c_int, [_P, _P, C.c_int, C.c_int64, _P, C.POINTER(ToaShared), _P, C.POINTER(ToaBounds), C.POINTER(ToaPrior),
+                                        C.POINTER(ToaOptions), C.POINTER(ToaResults), _P]),
+    "toa_jit_accumulate_shared": (C.c_int, [_P, _P, C.c_int, C.c_int64, _P, C.POINTER(ToaShared), _P, C.POINTER(ToaBounds), C.POINTER(ToaPrior), C.c_int,
+                                            _P, _P, _P, _P]),
     "toa_gd_options_default": (None, [C.POINTER(ToaGdOptions)]),
     "toa_jit_gd_run": (C.c_int, [_P, _P, C.c_int, C.c_int64, _P, _P, C.POINTER(ToaOptions), C.POINTER(ToaGdOptions), C.POINTER(ToaResults), _P]),
     "toa_lbfgs_options_default": (None, [C.POINTER(ToaLbfgsOptions)]),

@@ -22,7 +22,7 @@ import torch
 
 from . import _capi
 from ._capi import (F32, F64, MODEL_DENSE_ROW_AD, MODEL_DENSE_ROW_NATURAL, MODEL_TESTFN, MODEL_MAHA_PRIOR, MODEL_SE3_PRIOR, MODEL_CIRCLE_FIT, MODEL_DENSE_ROW, MODEL_DENSE_ROW_AD6, MODEL_GAUSSIAN_PRIOR, MODEL_SE3_REPROJ,
-                    MODEL_SQRT2, ToaBaConstant, ToaBounds, ToaGdOptions, ToaJitSpec, ToaLbfgsOptions, ToaOptions, ToaPrior, ToaResults, check)
+                    MODEL_SQRT2, ToaBaConstant, ToaBounds, ToaGdOptions, ToaJitSpec, ToaLbfgsOptions, ToaOptions, ToaPrior, ToaResults, ToaShared, check)
 
 
 class StopReason(enum.IntEnum):  # include/tinyopt/stop_reasons.h:14-43
@@ -287,6 +287,7 @@ class _Model:
     loss, th = None, 0.0
     prior = None        # (mu, W, rows): rows = 0 the diagonal form
     bounds = None       # (lo, hi)
+    shared = None       # a bound run-time model with shared_scalars: the batch's one table [items, shared_scalars]
     ragged = large_n = header_l2 = False
     xdim = functools.cached_property(lambda self: self.n)   # scalars of x per problem, where a model does not say
 
@@ -469,6 +470,9 @@ class _JitBatch(_LossMixin, _PriorMixin, _BoundsMixin):
     def _extras(self):
         """(the key (ragged, extra) of _JIT_ENTRIES, the extra's arguments): the bounds pod and the prior's or NULL, or the prior pod, or
         nothing.  A byref holds its pod, so the tuple keeps them alive for the call."""
+        if self.shared is not None:   # (uniform only) the table stands in _head, behind the data; bounds and prior follow x, each or NULL
+            return (False, "shared"), (C.byref(self._bounds_pod()) if self.bounds is not None else None,
+                                       C.byref(self._prior_pod()) if self.prior is not None else None)
         if self.bounds is not None:
             return (self.ragged, "bounds"), (C.byref(self._bounds_pod()), C.byref(self._prior_pod()) if self.prior is not None else None)
         if self.prior is not None:
@@ -477,11 +481,11 @@ class _JitBatch(_LossMixin, _PriorMixin, _BoundsMixin):
 
 
 _JIT_ENTRIES = {   # entry family -> (ragged, extra) -> the library entry
-    "lm_run": {(False, "prior"): "toa_jit_lm_run_prior", (False, "bounds"): "toa_jit_lm_run_bounds",
+    "lm_run": {(False, "shared"): "toa_jit_lm_run_shared", (False, "prior"): "toa_jit_lm_run_prior", (False, "bounds"): "toa_jit_lm_run_bounds",
                (True, None): "toa_jit_lm_run_ragged", (True, "prior"): "toa_jit_lm_run_ragged_prior", (True, "bounds"): "toa_jit_lm_run_ragged_bounds"},
     "gd_run": {(False, None): "toa_jit_gd_run", (True, None): "toa_jit_gd_run_ragged"},
     "lbfgs_run": {(False, None): "toa_jit_lbfgs_run", (True, None): "toa_jit_lbfgs_run_ragged"},
-    "accumulate": {(False, None): "toa_jit_accumulate", (False, "prior"): "toa_jit_accumulate_prior", (False, "bounds"): "toa_jit_accumulate_bounds",
+    "accumulate": {(False, None): "toa_jit_accumulate", (False, "shared"): "toa_jit_accumulate_shared", (False, "prior"): "toa_jit_accumulate_prior", (False, "bounds"): "toa_jit_accumulate_bounds",
                    (True, None): "toa_jit_accumulate_ragged", (True, "prior"): "toa_jit_accumulate_ragged_prior",
                    (True, "bounds"): "toa_jit_accumulate_ragged_bounds"},
     "eval": {(False, None): "toa_jit_eval", (True, None): "toa_jit_eval_ragged"},
@@ -518,6 +522,11 @@ def _refuse_cost_ggn(what: str):
 
 def _is_cost_ggn(cost) -> bool:
     return cost.route == "jit" and getattr(cost.res, "kind", None) == "cost_ggn"
+
+
+def _refuse_shared(what: str):
+    raise ValueError(f"a model with a shared item table (shared_scalars > 0) runs in the uniform one-launch form through Optimize (LM / GN) and "
+                     f"accumulate only: {what}")
 
 
 def _refuse_ragged(what: str):
@@ -579,10 +588,17 @@ _REFUSALS = {
     ("cost_ggn", "lbfgs"): 'no L-BFGS: run the same cost as kind="cost_grad"',
     ("cost_ggn", "splits"): _NO_SPLITS, ("cost_ggn", "host"): _NO_HOST, ("cost_ggn", "Optimizer"): _NO_STEPPING,
     **{("cost_ggn", what): f"no {what} (it has no residual rows: accumulate returns its value, its gradient and its Hessian)" for what in ("Eval", "CalculateJac")},
+    # a model with a shared item table (shared_scalars > 0): LM / GN and accumulate in the uniform one-launch form
+    ("shared", "splits"): _NO_SPLITS, ("shared", "host"): _NO_HOST, ("shared", "gd"): _NO_GD, ("shared", "lbfgs"): "no L-BFGS",
+    ("shared", "Optimizer"): _NO_STEPPING,
+    ("shared", "CheckGradient"): 'no CheckGradient (compare accumulate of a kind="accumulate" body with accumulate of its residuals under '
+                                 'diff="central", both with the table)',
+    **{("shared", what): f"no {what} (its kernels read replicated items: bind the table copied into every problem's items)" for what in ("Eval", "CalculateJac")},
 }
 _REFUSE_AS = {"ragged": _refuse_ragged, "bounds": _refuse_bounds, "prior": _refuse_prior, "large_n": _refuse_large_n, "cost_hess": _refuse_cost_hess,
-              "cost_ggn": _refuse_cost_ggn}
-_OPTIMIZE_REFUSES = (("cost_ggn", "lbfgs"), ("cost_ggn", "gd"), ("cost_ggn", "splits"), ("cost_ggn", "host"),
+              "cost_ggn": _refuse_cost_ggn, "shared": _refuse_shared}
+_OPTIMIZE_REFUSES = (("shared", "lbfgs"), ("shared", "gd"), ("shared", "splits"), ("shared", "host"),
+                     ("cost_ggn", "lbfgs"), ("cost_ggn", "gd"), ("cost_ggn", "splits"), ("cost_ggn", "host"),
                      ("cost_hess", "lbfgs"), ("bounds", "lbfgs"), ("prior", "lbfgs"), ("large_n", "lbfgs"), ("not_cost", "lbfgs"),
                      ("lbfgs_cost", "host"), ("lbfgs_cost", "splits"), ("lbfgs_cost", "grad_clipping"), ("lbfgs_cost", "lbfgs.history"),
                      ("lbfgs_cost", "lbfgs.c1"), ("lbfgs_cost", "lbfgs.shrink"),
@@ -591,9 +607,9 @@ _OPTIMIZE_REFUSES = (("cost_ggn", "lbfgs"), ("cost_ggn", "gd"), ("cost_ggn", "sp
                      ("bounds", "splits"), ("bounds", "host"), ("bounds", "gd"), ("prior", "splits"), ("prior", "host"), ("prior", "gd"),
                      ("large_n", "splits"), ("large_n", "host"), ("large_n", "gd"), ("large_n", "capture"), ("numeric", "host"), ("numeric", "splits"),
                      ("gd_cost", "host"), ("gd_cost", "splits"), ("stepping", "out with host controls"))
-_OPTIMIZER_REFUSES = tuple((who, "Optimizer") for who in ("lbfgs", "cost_hess", "cost_ggn", "ragged", "bounds", "prior", "numeric", "large_n"))
-_CHECK_GRADIENT_REFUSES = tuple((who, "CheckGradient") for who in ("bounds", "prior", "ragged", "large_n"))
-_ROWS_REFUSES = {what: (("cost_hess", what), ("cost_ggn", what), ("bounds", what), ("prior", what)) for what in ("Eval", "CalculateJac")}
+_OPTIMIZER_REFUSES = tuple((who, "Optimizer") for who in ("shared", "lbfgs", "cost_hess", "cost_ggn", "ragged", "bounds", "prior", "numeric", "large_n"))
+_CHECK_GRADIENT_REFUSES = tuple((who, "CheckGradient") for who in ("shared", "bounds", "prior", "ragged", "large_n"))
+_ROWS_REFUSES = {what: (("shared", what), ("cost_hess", what), ("cost_ggn", what), ("bounds", what), ("prior", what)) for what in ("Eval", "CalculateJac")}
 
 
 def _who(cost, gd: bool = False, lbfgs: bool = False) -> set:
@@ -606,6 +622,8 @@ def _who(cost, gd: bool = False, lbfgs: bool = False) -> set:
         who.add("prior")
     if cost.large_n:
         who.add("large_n")
+    if cost.shared is not None:
+        who.add("shared")
     if cost.route == "jit" and cost.res.diff != "ad":
         who.add("numeric")
     if gd and cost.route == "jit" and cost.res.kind in JitResidual.COST_KINDS:
@@ -917,6 +935,24 @@ class JitResidual:
     evaluations of the body per item and pass; no ``splits`` and no host controls (stop callbacks, max_duration_ms, the log line).
     ``CheckGradient(model, x)`` compares the derivatives of ANY model with those differences.
 
+    Shared item tables — ``shared_scalars=k``: the body sees one more array, ``s[j]`` for ``0 <= j < k`` — for
+    item i of EVERY problem row i of ONE table ``[items, k]`` handed over by ``bind(data, shared=table)``: one design matrix for a GLM
+    per gene, one time axis for a curve fit per pixel, one map for many poses.  ``p[j]`` stays the item's own scalars
+    (``item_scalars=0`` is legal beside a table), ``h[j]`` the header; the caller replicates nothing, and the rows are staged into LDS
+    beside the private items (expected to come from the L2 after their first reader; not measured with counters).  ``kind="residual"`` (Jets or ``diff=``), ``"accumulate"`` and
+    ``"cost_ggn"``, Euclidean parameters; such a model is a row model at every n up to 63.  ``Optimize`` (LM / GN) and ``accumulate``
+    take it, with ``with_loss`` / ``with_prior`` / ``with_bounds`` as the kind allows; ``bind_ragged``, ``splits``, ``keep_order``, the
+    stepping ``Optimizer``, host controls, ``Eval`` / ``CalculateJac``, ``CheckGradient``, GradientDescent / L-BFGS, manifolds, the
+    other cost kinds and ``large_n`` are refused with a sentence.  Logistic regression at n = 50 on one design matrix::
+
+        glm = ta.JitResidual('''
+            T z = 0; for (int j = 0; j < 50; ++j) z += s[j] * x[j];
+            const T y = p[0], e = exp(-y * z), sg = T(1) / (T(1) + e);
+            c = log(T(1) + e);
+            if (want_grad) { gs = -y * (T(1) - sg); hs = sg * (T(1) - sg); for (int a = 0; a < 50; ++a) J[a] = s[a]; }''',
+            n=50, item_scalars=1, shared_scalars=50, kind="cost_ggn", dtype=torch.float32)
+        out = ta.Optimize(w, glm.bind(labels[:, :, None], shared=X), ta.Options())   # labels [P, items], X [items, 50]
+
     Beyond 63 parameters — ``large_n=True`` compiles the model for the launch-per-phase pipeline of the wide problems
     (``DenseRowNatural``'s: a rows kernel over the body, the Gram on the matrix cores, the library's own LDL^T / blocked Cholesky)
     instead of a wavefront per problem: ``n`` up to 1024 in float32 and 512 in float64 (1 .. 63 is allowed too, so that one text can
@@ -935,7 +971,8 @@ class JitResidual:
 
     def __init__(self, body: str, n: int, item_scalars: int, residuals_per_item: int = 1, header_scalars: int = 0,
                  dtype: torch.dtype = torch.float64, ctx: Optional["Context"] = None, manifold: str = "euclid", kind: str = "residual",
-                 plus_body: Optional[str] = None, x_scalars: int = 0, diff: str = "ad", diff_h: float = 0.0, large_n: bool = False):
+                 plus_body: Optional[str] = None, x_scalars: int = 0, diff: str = "ad", diff_h: float = 0.0, large_n: bool = False,
+                 shared_scalars: int = 0):
         """Round 5 — ``manifold="user"``: the caller's own parameter container (the reference's traits::params_trait<T>, traits.h:103-359).
         x is stored as ``x_scalars`` scalars per problem ([P, x_scalars]), ``n`` is the dimension of its tangent and ``plus_body``
         is the body of ``template <class S> void plus(const T* x, const S* d, S* xp)``: xp = x (+) d, written over the scalar type
@@ -950,6 +987,16 @@ class JitResidual:
             raise ValueError(f"unknown diff {diff!r}; one of {sorted(self.DIFFS)}")
         self.diff, self.diff_h = diff, float(diff_h)
         self.large_n = bool(large_n)
+        self.kS = int(shared_scalars)
+        if self.kS:   # (the library refuses the same, toa_model_compile_ex: here before anything is compiled)
+            if not 0 < self.kS <= 512:
+                raise ValueError(f"shared_scalars must be in 0 .. 512 (0 = no shared item table), not {self.kS}")
+            if kind in self.COST_KINDS or kind == "cost_hess":
+                _refuse_shared(f'kind="residual", "accumulate" and "cost_ggn" take a table (the row models stage it), not kind={kind!r}')
+            if manifold != "euclid":
+                _refuse_shared(f"Euclidean parameters only, not manifold={manifold!r}")
+            if self.large_n:
+                _refuse_shared("no large_n")
         if kind == "cost_hess":   # (the library refuses the same, toa_model_compile_ex: here before anything is compiled)
             if manifold != "euclid":
                 _refuse_cost_hess(f"Euclidean parameters only, not manifold={manifold!r}")
@@ -994,6 +1041,7 @@ class JitResidual:
         spec.manifold, spec.kind = self.MANIFOLDS[manifold], self.KINDS[kind]
         spec.diff, spec.diff_h = self.DIFFS[diff], self.diff_h
         spec.large_n = 1 if self.large_n else 0
+        spec.shared_scalars = self.kS
         if manifold == "user":
             if not plus_body or int(x_scalars) < 1:
                 raise ValueError('manifold="user" needs plus_body (the body of x (+) d) and x_scalars')
@@ -1017,10 +1065,28 @@ class JitResidual:
         """Where compiled code objects are kept (default: $XDG_CACHE_HOME/tinyopt_amd or ~/.cache/tinyopt_amd); "" = no cache."""
         check((ctx or default_context()).lib.toa_jit_set_cache_dir(None if path is None else path.encode()))   # None: back to the default
 
-    def bind(self, data: Optional[torch.Tensor], header: Optional[torch.Tensor] = None, items: int = 1) -> "JitModel":
+    def bind(self, data: Optional[torch.Tensor], header: Optional[torch.Tensor] = None, items: int = 1,
+             shared: Optional[torch.Tensor] = None) -> "JitModel":
         """data: [P, items, item_scalars] (and header: [P, header_scalars]) on the GPU -> the ``cost`` of Optimize(x, cost).
-        data = None for a functor with item_scalars = 0 (e.g. a pose prior: everything is in the header)."""
-        return JitModel(self, data, header, items)
+        data = None for a functor with item_scalars = 0 (e.g. a pose prior: everything is in the header).
+        shared: [items, shared_scalars] on the GPU, the model's dtype — the ONE table every problem reads (row i beside item i's own
+        scalars, as ``s[k]`` in the body): required by a model with ``shared_scalars``, refused by one without.  With
+        ``item_scalars = 0`` the rule above holds: ``bind(None, header=..., items=..., shared=table)`` — the header carries P."""
+        kS = getattr(self, "kS", 0)
+        if shared is None:
+            if kS:
+                raise ValueError(f"bind: a model with shared_scalars = {kS} needs shared=, the batch's [items, {kS}] table")
+            return JitModel(self, data, header, items)
+        if not kS:
+            raise ValueError("bind: shared= is the table of a model with shared_scalars > 0; this model has none")
+        m = JitModel(self, data, header, items)
+        if not isinstance(shared, torch.Tensor) or tuple(shared.shape) != (m.items, kS):
+            raise ValueError(f"bind: shared must be an [items, shared_scalars] = [{m.items}, {kS}] tensor, not "
+                             f"{list(shared.shape) if isinstance(shared, torch.Tensor) else type(shared).__name__}")
+        if shared.dtype != self.dtype or shared.device != m.packed.device:
+            raise ValueError(f"bind: shared must have the model's dtype {self.dtype} on the data's device {m.packed.device}, not {shared.dtype} on {shared.device}")
+        m.shared = shared.contiguous()
+        return m
 
     def bind_ragged(self, data: torch.Tensor, counts=None, offsets=None, header: Optional[torch.Tensor] = None) -> "RaggedJitModel":
         """A RAGGED batch: every problem has its own item count.  data: [total_items, item_scalars] on the GPU, the items of all
@@ -1032,6 +1098,8 @@ class JitResidual:
             _refuse_cost_hess("no ragged batches (bind_ragged)")
         if self.kind == "cost_ggn":
             _refuse_cost_ggn("no ragged batches (bind_ragged)")
+        if getattr(self, "kS", 0):
+            _refuse_shared("no ragged batches (bind_ragged)")
         return RaggedJitModel(self, data, counts, offsets, header)
 
     def stats_prior(self, ragged: bool = False) -> dict:
@@ -1094,10 +1162,18 @@ class JitModel(_JitBatch):
         return self.packed.device
 
     def _head(self, ctx: "Context", x: torch.Tensor) -> tuple:
+        if self.shared is not None:   # (the *_shared entries: the table between the data and x)
+            return (ctx.h, self.res._h, self.items, x.shape[0], self.packed.data_ptr(), C.byref(self._shared_pod()), x.data_ptr())
         return (ctx.h, self.res._h, self.items, x.shape[0], self.packed.data_ptr(), x.data_ptr())
+
+    def _shared_pod(self):
+        pod = ToaShared()
+        pod.table_dev, pod.rows = self.shared.data_ptr(), self.shared.shape[0]
+        return pod
 
     @property
     def algorithmic_bytes_per_pass(self) -> int:
+        """Per problem: its own items (the shared table is read once for the whole batch, not per problem)."""
         return self.packed.shape[1] * self.packed.element_size()
 
 
@@ -1483,7 +1559,7 @@ def Optimize(x: torch.Tensor, cost, options: Optional[Options] = None, *, histor
             check(lib.toa_lm_run_split(ctx.h, cost.model_id, _dtype_code(x.dtype), cost.n, cost.m, x.shape[0], cost.packed.data_ptr(), x.data_ptr(),
                                        C.byref(pod), C.byref(res), out.counters.data_ptr(), int(splits)))
         return out
-    if route == "jit" and not (gd_run or lbfgs_run or cost.ragged) and cost.bounds is None and cost.prior is None:
+    if route == "jit" and not (gd_run or lbfgs_run or cost.ragged) and cost.bounds is None and cost.prior is None and cost.shared is None:
         # the plain uniform run-time model, spelled out for the same reason (and the only one with a row-split form)
         if splits is None:
             check(lib.toa_jit_lm_run(ctx.h, cost.res._h, cost.items, x.shape[0], cost.packed.data_ptr(), x.data_ptr(),

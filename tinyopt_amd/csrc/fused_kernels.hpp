@@ -86,6 +86,16 @@ struct BoundsFusedParams {
   BoundsArgs bounds;
 };
 
+// ... and of a launch of a model with a shared item table (shared.hpp), with or without a prior and bounds: the bounds block, then
+// the table.  Only a code object built with TOA_SHARED reads that far.
+struct SharedFusedParams {
+  FusedParams f;
+  RaggedArgs ragged;
+  PriorArgs prior;
+  BoundsArgs bounds;
+  SharedArgs shared;
+};
+
 template <typename M, typename = void>
 struct ModelStageBytes { static constexpr size_t value = 0; };
 template <typename M>
@@ -167,6 +177,9 @@ __global__ void __launch_bounds__(64 * ModelWaves<Model>::value) TOA_FUSED_ATTR 
 #endif
 #ifdef TOA_BOUNDS
   model.set_bounds(reinterpret_cast<const BoundsFusedParams*>(prm_g)->bounds, L.M, L.LD);
+#endif
+#ifdef TOA_SHARED
+  model.set_shared(reinterpret_cast<const SharedFusedParams*>(prm_g)->shared);
 #endif
   if constexpr (ModelStageBytes<Model>::value > 0) model.stage = reinterpret_cast<unsigned char*>(smem) + size_t(wave) * prm_g->lds_per_wave + prm_g->stage_off;
   T* X = static_cast<T*>(prm_g->x);
@@ -276,7 +289,7 @@ __global__ void __launch_bounds__(64 * ModelWaves<Model>::value) TOA_FUSED_ATTR 
 template <typename Model>
 __global__ void __launch_bounds__(256) accumulate_kernel(const void* data_, const void* x_, long long P, int n, int m,
                                                          int want_grad, void* g_, void* H_, double* cost, int* nres,
-                                                         int lds_per_wave, int loss, double loss_th2 TOA_RAGGED_KARG TOA_PRIOR_KARG TOA_BOUNDS_KARG) {
+                                                         int lds_per_wave, int loss, double loss_th2 TOA_RAGGED_KARG TOA_PRIOR_KARG TOA_BOUNDS_KARG TOA_SHARED_KARG) {
   using T = typename Model::Scalar;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -286,6 +299,9 @@ __global__ void __launch_bounds__(256) accumulate_kernel(const void* data_, cons
   model.set_loss(loss, loss_th2);
 #ifdef TOA_RAGGED
   model.set_ragged(rag);
+#endif
+#ifdef TOA_SHARED
+  model.set_shared(shr);
 #endif
   WaveLds<T> L = WaveLds<T>::carve(model_bind_stage(model, smem + size_t(wave) * lds_per_wave, n), n);
 #ifdef TOA_PRIOR

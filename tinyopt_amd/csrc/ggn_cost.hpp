@@ -57,19 +57,40 @@ struct GgnRowFunctor {
       r[0] = T(0);
     }
   }
+  // ... of a body with a shared item table (shared.hpp): `s` is the item's row of it, after p
+  static constexpr int kS = FunctorShared<F>::value;
+  template <bool want_grad>
+  static __device__ __forceinline__ void eval_item(const T* x, const T* h, const T* p, const T* s, T& c, T* r, T (*J)[kN]) {
+    T gs = T(0), hs = T(0);
+    if constexpr (want_grad) {
+      F::template eval_ggn<true>(x, h, p, s, c, gs, hs, J[0]);
+      const T wmin = GgnWmin<T>::value;
+      const T w = hs <= wmin ? wmin : hs;   // (a NaN compares false: it stays)
+      const T sq = sqrt(w);
+      r[0] = gs / sq;
+#pragma unroll
+      for (int a = 0; a < kN; ++a) J[0][a] *= sq;
+    } else {
+      F::template eval_ggn<false>(x, h, p, s, c, gs, hs, static_cast<T*>(nullptr));
+      r[0] = T(0);
+    }
+  }
 };
 
 // The Accumulate seam (toa_jit_accumulate on a TOA_JIT_COST_GGN model): accumulate_kernel's arguments and its loop, with H_ optional —
 // g [P][n], the full symmetric H [P][n][n] when H_ is not null, cost [P] = sum_i c_i, nres [P] = 1.
 template <typename Model>
 __global__ void __launch_bounds__(256) ggn_accumulate_kernel(const void* data_, const void* x_, long long P, int n, int m, int want_grad, void* g_,
-                                                             void* H_, double* cost, int* nres, int lds_per_wave, int, double) {
+                                                             void* H_, double* cost, int* nres, int lds_per_wave, int, double TOA_SHARED_KARG) {
   using T = typename Model::Scalar;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const T* X = static_cast<const T*>(x_);
   Model model;
   model.init(n, m, data_);
+#ifdef TOA_SHARED
+  model.set_shared(shr);
+#endif
   WaveLds<T> L = WaveLds<T>::carve(model_bind_stage(model, smem + size_t(wave) * lds_per_wave, n), n);
   for (long long p = (long long)blockIdx.x * 4 + wave; p < P; p += (long long)gridDim.x * 4) {
     wave_sync();

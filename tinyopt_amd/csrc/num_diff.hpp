@@ -38,6 +38,7 @@
 #pragma once
 #include <type_traits>
 #include "wave_utils.hpp"
+#include "shared.hpp"   // FunctorShared: a body with a shared item table
 
 #ifndef TOA_AD_CW   // the chunk width of AdRowFunctor's Jets (row_model.hpp): the same columns per chunk here, under the same -DTOA_AD_CW=k
 #define TOA_AD_CW 12
@@ -131,6 +132,39 @@ struct NumRowFunctor {
           for (int q = 0; q < kR; ++q) {
 #pragma unroll
             for (int t = 0; t < cw; ++t) J[q][c0 + t] = (t == s) ? dq[q] : J[q][c0 + t];   // (J[q][c0 + s] with the running s would be scratch memory)
+          }
+        }
+      });
+    }
+  }
+  // ... of a body with a shared item table (shared.hpp): `sh` is the item's row of it, after p — data, not
+  // perturbed.  Residual bodies only (a numeric MODEL never wraps an accumulate body, and such a model has no checker's twin).
+  static constexpr int kS = FunctorShared<F>::value;
+  template <bool want_grad>
+  static __device__ __forceinline__ void eval_manual(const T* x, const T* hd, const T* p, const T* sh, T* r, T (*J)[kN]) {
+    T r0[kR];
+    F::template eval<T>(x, hd, p, sh, r0);
+#pragma unroll
+    for (int q = 0; q < kR; ++q) r[q] = r0[q];
+    if constexpr (want_grad) {
+      const T hh = T(HS::value);
+      static_for<kChunks>([&](auto cc) __attribute__((always_inline)) {
+        constexpr int c0 = decltype(cc)::value * kCW;
+        constexpr int cw = kN - c0 < kCW ? kN - c0 : kCW;
+#pragma unroll
+        for (int q = 0; q < kR; ++q) {
+#pragma unroll
+          for (int t = 0; t < cw; ++t) J[q][c0 + t] = T(0);
+        }
+#pragma unroll 1
+        for (int s = 0; s < cw; ++s) {
+          T dq[kR];
+          num_diff_column<T, METHOD>(x, c0 + s, hh, r0, dq,
+                                     [&](const auto& xa, T (&out)[kR]) __attribute__((always_inline)) { F::template eval<T>(xa, hd, p, sh, out); });
+#pragma unroll
+          for (int q = 0; q < kR; ++q) {
+#pragma unroll
+            for (int t = 0; t < cw; ++t) J[q][c0 + t] = (t == s) ? dq[q] : J[q][c0 + t];
           }
         }
       });

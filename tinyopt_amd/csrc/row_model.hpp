@@ -23,6 +23,8 @@
 // fp64, n = 50 — tools/isa_lint.py on the run-time compiler's output).  A library cannot lint code it has not seen; a prefetch
 // that owns no register cannot be broken by it.
 #pragma once
+#include "shared.hpp"   // FunctorShared, SharedArgs: a model with a shared item table
+#include "row_stage_geom.hpp"   // RowStageGeom: the stage's geometry, shared with the host launchers
 #ifndef TOA_ROW_SINGLE
 #define TOA_ROW_SINGLE 1   // accumulate passes use ONE region of the stage (fetch, wait, compute: every lane an item) for every functor;
                            // 0 = the ring for functors that are not compute-bound (A/B: C4 as text 11.4 -> 10.8 ms with 1, profiles/r06_ab_log.md)
@@ -35,76 +37,6 @@
 #endif
 
 namespace toa {
-
-// Geometry of a row model's super-step: a function of (sizeof(T), kN, kR, kD) only, evaluated by the device templates and by
-// the host launchers (jit.hip, kernels.hpp) alike.
-struct RowStageGeom {
-  int items2;  // items per super-step, one per lane, when the stage is a RING of `nbuf` regions (the items of the next nbuf - 1
-               // super-steps are on their way while this one is consumed): memory-bound passes — a functor with the user's own
-               // Jacobian, every cost-only pass
-  int nbuf;    // regions of that ring
-  int items1;  // ... when it is ONE region (fetch, wait, compute): the accumulate pass of a compute-bound functor (AD), which
-               // wants every lane busy more than it wants the prefetch (0 = the model has no such pass)
-  int ps;      // item stride in the raw image, elements (>= kD)
-  int rsp;     // row stride of the [J | r] image, elements (>= the packed row)
-  int bytes;   // the wave's LDS stage
-  int table_off;   // where the model's own `extra` bytes begin, behind the regions (AdRowFunctor on a manifold: the Jets of x (+) d)
-  // Both images are read and written a ROW (an item) PER LANE: a stride of 16 bytes x an odd number makes every 16-byte access of
-  // sixteen consecutive lanes hit sixteen different bank quads (ds_read_b128 / ds_write_b128 without conflicts) and keeps every
-  // row 16-byte aligned.
-  static __host__ __device__ constexpr int stride16(int elems, int sz) {
-    int q = (elems * sz + 15) / 16;
-    if (!(q & 1)) ++q;
-    return q * 16 / sz;
-  }
-  // bytes of one region for `it` items: their raw image, then the [J | r] image over it
-  static __host__ __device__ constexpr int region(int it, int ps, int rsp, int kR, int sz) {
-    const int raw = it * ps * sz, img = ((it * kR + 3) & ~3) * rsp * sz;
-    return (raw > img ? raw : img);
-  }
-  // What a wave's stage may take.  With `waves` = 2 workgroups of four waves on a compute unit a wave has 160 KiB / 8 = 20 KiB of
-  // LDS, with 3 (twelve waves) 13.3 KiB; the part of its carve that is alive during a pass (x, g, the diagonal, the last step, the
-  // memo's x, the state and option blocks) takes 5 x 64 scalars + ~0.5 KiB of that.
-  static __host__ __device__ constexpr int budget(int sz, int waves) { return 160 * 1024 / (4 * waves) - 320 * sz - 512; }
-  // Ring depth (TOA_ROW_NBUF) and resident workgroups per compute unit the geometry is sized for (TOA_ROW_WAVES): A/B arms of
-  // the run-time build (profiles/r06_ab_log.md); jit.hip reads the same two values out of $TOA_JIT_FLAGS for its LDS sizing.
-#ifndef TOA_ROW_NBUF
-#define TOA_ROW_NBUF 2
-#endif
-#ifndef TOA_ROW_WAVES
-#define TOA_ROW_WAVES 2
-#endif
-  static __host__ __device__ constexpr RowStageGeom make(int sz, int n, int kR, int kD, bool compute_bound, int nbuf = TOA_ROW_NBUF,
-                                                        int waves = TOA_ROW_WAVES, int extra = 0) {
-    const int rem = n & 15;
-    const bool thin = n >= 16 && rem + 1 <= 4;
-    const int nbm = thin ? (n >> 4) : (n + 16) / 16;
-    const int rs = thin ? 16 * nbm + rem + 1 : nbm * ((n + nbm) / nbm);
-    RowStageGeom g{};
-    g.rsp = stride16(rs, sz);
-    g.ps = kD > 0 ? stride16(kD, sz) : 0;
-    const int itmax = 64 / kR;           // rows of a super-step <= 64
-    const int bud = budget(sz, waves) - extra;
-    g.nbuf = nbuf;
-    int it = itmax;                      // the largest multiple of 4 (one Gram step = four rows) whose ring fits; else 2, 1
-    if (it >= 4) it &= ~3;
-    while (it > 1 && g.nbuf * region(it, g.ps, g.rsp, kR, sz) > bud) it = it > 4 ? it - 4 : it >> 1;
-    g.items2 = it;
-    g.bytes = g.nbuf * region(it, g.ps, g.rsp, kR, sz);
-    g.items1 = 0;
-    if (compute_bound) {
-      it = itmax;
-      if (it >= 4) it &= ~3;
-      while (it > 1 && region(it, g.ps, g.rsp, kR, sz) > bud) it = it > 4 ? it - 4 : it >> 1;
-      g.items1 = it;
-      if (region(it, g.ps, g.rsp, kR, sz) > g.bytes) g.bytes = region(it, g.ps, g.rsp, kR, sz);
-    }
-    g.bytes = (g.bytes + 15) & ~15;
-    g.table_off = g.bytes;
-    g.bytes += (extra + 15) & ~15;
-    return g;
-  }
-};
 
 // Forward-mode AD as a manual-Jacobian functor: F::eval, written once over the scalar type (docs/API.md:21-35), is run on
 // Jet<T, CW> once per CHUNK of CW parameters — seeds x_jet[j].v[j - c0] = 1 (optimize_autodiff.h:56-69) — and J.row = res.v
@@ -227,6 +159,29 @@ struct AdRowFunctor {
       });
     }
   }
+  // ... of a functor with a shared item table (FunctorShared; Euclidean only): `sh` is the item's row of it, plain T like p
+  static constexpr int kS = FunctorShared<F>::value;
+  static_assert(kS == 0 || MANIFOLD == 0, "a shared item table: Euclidean parameters only");
+  template <bool want_grad>
+  static __device__ __forceinline__ void eval_manual(const T* x, const T* h, const T* p, const T* sh, T* r, T (*J)[kN]) {
+    if constexpr (!want_grad) {
+      F::template eval<T>(x, h, p, sh, r);
+    } else {
+      static_for<kChunks>([&](auto cc) __attribute__((always_inline)) {
+        constexpr int c0 = decltype(cc)::value * kCW;
+        ChunkSeededX<T, kCW> X{x, c0};
+        Jet<T, kCW> rr[kR];
+        F::template eval<Jet<T, kCW>>(X, h, p, sh, rr);
+#pragma unroll
+        for (int q = 0; q < kR; ++q) {
+          if constexpr (c0 == 0) r[q] = rr[q].a;
+#pragma unroll
+          for (int s = 0; s < kCW; ++s)
+            if (c0 + s < kN) J[q][c0 + s] = rr[q].v[s];
+        }
+      });
+    }
+  }
 };
 
 template <typename F, typename = void>
@@ -267,7 +222,10 @@ struct RowModel {
   static constexpr int kNmr = THIN ? 16 * NBM : kN;
   static constexpr int kRsm = THIN ? 16 * NBM : NBM * ((kN + NBM) / NBM);
   static constexpr int kRs = kRsm + THIN;
-  static constexpr RowStageGeom kGeom = RowStageGeom::make(int(sizeof(T)), kN, kR, kD, FunctorComputeBound<F>::value || TOA_ROW_SINGLE, TOA_ROW_NBUF, TOA_ROW_WAVES, kTableBytes);
+  // a shared item table (shared.hpp): row i of [items][kS] beside item i's private scalars, for every problem of the batch
+  static constexpr int kS = FunctorShared<F>::value;
+  static_assert(kS == 0 || (MANIFOLD == 0 && kTableBytes == 0), "a shared item table: Euclidean parameters only");
+  static constexpr RowStageGeom kGeom = RowStageGeom::make(int(sizeof(T)), kN, kR, kD, FunctorComputeBound<F>::value || TOA_ROW_SINGLE, TOA_ROW_NBUF, TOA_ROW_WAVES, kTableBytes, kS);
   static_assert(kGeom.items2 >= 1 && (kTableBytes == 0 || kGeom.items1 >= 4), "the Jets of x (+) d leave no room for the items in the wave's LDS stage");
   static constexpr int PS = kGeom.ps, RSP = kGeom.rsp;
   static constexpr size_t kStageBytes = size_t(kGeom.bytes);
@@ -276,6 +234,8 @@ struct RowModel {
   // arithmetic); straight from LDS otherwise, and for functors that index them with a running index
   static constexpr bool kXRegs = TOA_ROW_XREGS && MANIFOLD == 0 && !FunctorIndexed<F>::value && kN * int(sizeof(T)) <= 256;
   static constexpr bool kPRegs = !FunctorIndexed<F>::value && kD * int(sizeof(T)) <= 256;
+  static constexpr bool kSRegs = !FunctorIndexed<F>::value && kS * int(sizeof(T)) <= 256;   // the item's shared row, by the same rule
+  static constexpr int PSS = kGeom.pss;
 
   __device__ __forceinline__ void plus_eq(WaveLds<T>& L, const T* dv, T sign, int n, int lane) const {
     if constexpr (MANIFOLD == 1) Se3Manifold<T>::plus_eq(L, dv, sign, n, lane);
@@ -301,6 +261,10 @@ struct RowModel {
     stage = nullptr;
   }
   __device__ __forceinline__ void set_loss(int kind, double t2) { loss = kind; th2 = T(t2); }
+#ifdef TOA_SHARED
+  const T* shared;       // the batch's shared table [items][kS] (a TOA_SHARED code object only: shared.hpp)
+  __device__ __forceinline__ void set_shared(const SharedArgs& a) { shared = static_cast<const T*>(a.table); }
+#endif
 #ifdef TOA_RAGGED
   // Ragged batches (ragged.hpp; the ragged code object of a run-time model only): the problem's range from the offsets array, its
   // header from a separate array; m (and the layout's padded row count) become the bound problem's, as a uniform launch of
@@ -338,24 +302,37 @@ struct RowModel {
   // of 16; its tail may read the first bytes of the next item into the padding).  Bounds: the descriptor ends with the pass's
   // items — beyond them zeros arrive, touching no memory.  M0 (the DMA's LDS base) is written in the statement that uses it and
   // put back.
+  // The SHARED image of a super-step (kS > 0) is made by the same pieces with ITEM_BYTES / STRIDE_BYTES those of a table row, from
+  // a descriptor over the table's rows of the pass, at `lds` = the region's address + the private image's bytes.
   static constexpr unsigned kItemBytes = unsigned(kD) * unsigned(sizeof(T)), kPsBytes = unsigned(PS) * unsigned(sizeof(T));
-  template <int IT, int V>
+  static constexpr unsigned kShItemBytes = unsigned(kS) * unsigned(sizeof(T)), kShPsBytes = unsigned(PSS) * unsigned(sizeof(T));
+  template <int IT, int V, unsigned ITEM_BYTES = kItemBytes, unsigned STRIDE_BYTES = kPsBytes>
   static __device__ __forceinline__ void dma_piece(const i32x4 rsrc, const int lane, const unsigned soff, const unsigned lds) {
-    constexpr unsigned kRawBytes = unsigned(IT) * kPsBytes;
+    constexpr unsigned kRawBytes = unsigned(IT) * STRIDE_BYTES;
     const unsigned o = unsigned(V) * 1024u + unsigned(lane) * 16u;           // this lane's byte of the image
-    const unsigned it = o / kPsBytes, w = o - it * kPsBytes;
-    const unsigned voff = (w < kItemBytes) ? it * kItemBytes + w : 0x80000000u;   // (a piece of pure padding fetches nothing)
+    const unsigned it = o / STRIDE_BYTES, w = o - it * STRIDE_BYTES;
+    const unsigned voff = (w < ITEM_BYTES) ? it * ITEM_BYTES + w : 0x80000000u;   // (a piece of pure padding fetches nothing)
     const unsigned la = unsigned(__builtin_amdgcn_readfirstlane(int(lds + unsigned(V) * 1024u)));
     unsigned keep;
     if ((V + 1) * 1024u <= kRawBytes || o < kRawBytes)
       asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 4\n\tbuffer_load_dwordx4 %1, %2, %4 offen lds\n\ts_mov_b32 m0, %0"
                    : "=&s"(keep) : "v"(voff), "s"(rsrc), "s"(la), "s"(soff) : "memory");
   }
-  template <int IT, int V0, int V1>   // pieces V0 <= V < V1
+  template <int IT, int V0, int V1, unsigned ITEM_BYTES = kItemBytes, unsigned STRIDE_BYTES = kPsBytes>   // pieces V0 <= V < V1
   static __device__ __forceinline__ void dma_issue(const i32x4 rsrc, const int lane, const unsigned soff, const unsigned lds) {
     if constexpr (V0 < V1) {
-      dma_piece<IT, V0>(rsrc, lane, soff, lds);
-      dma_issue<IT, V0 + 1, V1>(rsrc, lane, soff, lds);
+      dma_piece<IT, V0, ITEM_BYTES, STRIDE_BYTES>(rsrc, lane, soff, lds);
+      dma_issue<IT, V0 + 1, V1, ITEM_BYTES, STRIDE_BYTES>(rsrc, lane, soff, lds);
+    }
+  }
+  // the shared rows of super-step `ss` (its pieces behind the private ones of the same super-step: vector memory operations retire
+  // in order, so one count covers both sets) into the region at LDS byte address `lds`
+  template <int IT>
+  static __device__ __forceinline__ void dma_issue_shared(const i32x4 rsrc_s, const int lane, const int ss, const unsigned lds) {
+    if constexpr (kS > 0) {
+      constexpr int PFVS = (IT * int(kShPsBytes) + 1023) / 1024;
+      const unsigned soff = unsigned(__builtin_amdgcn_readfirstlane(int(unsigned(ss) * (unsigned(IT) * kShItemBytes))));
+      dma_issue<IT, 0, PFVS, kShItemBytes, kShPsBytes>(rsrc_s, lane, soff, lds + unsigned(IT) * kPsBytes);
     }
   }
   // 16-byte LDS accesses of a row that starts on a 16-byte boundary (the strides of RowStageGeom)
@@ -415,9 +392,10 @@ struct RowModel {
   template <bool WANT_H, int IT, int NBUF>
   __device__ __forceinline__ T pass(const T* __restrict__ xs, const int lane_in) {
     constexpr int ROWS = IT * kR, SPS = (ROWS + 3) / 4;   // rows / Gram steps of a super-step
-    constexpr int kRegion = RowStageGeom::region(IT, PS, RSP, kR, int(sizeof(T)));
+    constexpr int kRegion = RowStageGeom::region(IT, PS, RSP, kR, int(sizeof(T)), PSS);
     constexpr unsigned kSsBytes = unsigned(IT) * kItemBytes;     // a super-step's items in memory
     constexpr int PFV = (IT * int(kPsBytes) + 1023) / 1024;
+    constexpr int PFVS = (IT * int(kShPsBytes) + 1023) / 1024;   // pieces of the shared image (0 without a shared table)
     static_assert(ROWS <= 64 && kRegion % 16 == 0 && size_t(NBUF * kRegion) <= kStageBytes, "geometry");
     // A/B arm, measured and NOT the default (-DTOA_ROW_DMA_SPREAD=1): the next super-step's pieces issued BETWEEN this one's Gram
     // steps instead of in front of the functor (an LDS-DMA piece issued into a full queue stalls its wave; behind a step's
@@ -440,6 +418,13 @@ struct RowModel {
     const T* const items = d + F::kH + size_t(it0) * kD;
 #endif
     const i32x4 rsrc = make_rsrc(items, unsigned(nit) * unsigned(kD) * unsigned(sizeof(T)));
+#ifdef TOA_SHARED
+    // rows [it0, it0 + nit) of the shared table: the descriptor ends with the pass's rows, as the items' does
+    const i32x4 rsrc_s = make_rsrc(shared + size_t(it0) * kS, unsigned(nit) * kShItemBytes);
+#else
+    static_assert(kS == 0, "a functor with a shared item table needs a TOA_SHARED build");
+    const i32x4 rsrc_s = rsrc;   // (never read: dma_issue_shared is empty without a table)
+#endif
     unsigned char* const stg = static_cast<unsigned char*>(__builtin_assume_aligned(stage, 16));
     const unsigned lds0 = unsigned(reinterpret_cast<size_t>((__attribute__((address_space(3))) unsigned char*)(stg)));
     if (WANT_H) gram.clear();
@@ -456,6 +441,7 @@ struct RowModel {
       static_for<NBUF - 1>([&](auto bc) __attribute__((always_inline)) {
         constexpr int b = decltype(bc)::value;
         dma_issue<IT, 0, PFV>(rsrc, lane, unsigned(__builtin_amdgcn_readfirstlane(int(unsigned(b) * kSsBytes))), lds0 + unsigned(b * kRegion));
+        if constexpr (kS > 0) dma_issue_shared<IT>(rsrc_s, lane, b, lds0 + unsigned(b * kRegion));
       });
     }
     const bool active = THIN > 0 || c * NBM < kRsm;
@@ -469,13 +455,15 @@ struct RowModel {
         const int prv = cur == 0 ? (NBUF - 1) * kRegion : cur - kRegion;
         nxt_soff = unsigned(__builtin_amdgcn_readfirstlane(int(unsigned(ss + NBUF - 1) * kSsBytes)));
         nxt_lds = lds0 + unsigned(__builtin_amdgcn_readfirstlane(prv));
-        static_assert((NBUF - 2) * PFV < 64, "vmcnt is a 6-bit counter");
-        asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" :: "n"((NBUF - 2) * PFV) : "memory");
+        static_assert((NBUF - 2) * (PFV + PFVS) < 64, "vmcnt is a 6-bit counter");
+        asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" :: "n"((NBUF - 2) * (PFV + PFVS)) : "memory");
+        if constexpr (kS > 0) dma_issue_shared<IT>(rsrc_s, lane, ss + NBUF - 1, nxt_lds);   // (never spread: in front of the private pieces of its super-step)
         if constexpr (!kSpread) dma_issue<IT, 0, PFV>(rsrc, lane, nxt_soff, nxt_lds);
       } else {
         // ---- one region: fetch, wait (the SIMD's other waves cover the round trip of a functor that is the bound anyway)
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         dma_issue<IT, 0, PFV>(rsrc, lane, unsigned(__builtin_amdgcn_readfirstlane(int(unsigned(ss) * kSsBytes))), lds0);
+        if constexpr (kS > 0) dma_issue_shared<IT>(rsrc_s, lane, ss, lds0);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       }
       wave_sync();
@@ -494,6 +482,16 @@ struct RowModel {
         T pl[kPRegs ? (kD ? kD : 1) : 1];
         if constexpr (kPRegs) lds_read_row<kD>(pl, pi);
         const T* const p = kPRegs ? pl : pi;
+        // the item's row of the shared table: behind the IT private items of the region, read like them
+        // (nothing of it exists for a functor without a table)
+        T sl[(kSRegs && kS > 0) ? kS : 1];
+        const T* sp = nullptr;
+        if constexpr (kS > 0) {
+          const T* const si = S + size_t(IT) * PS + size_t(lane) * PSS;
+          if constexpr (kSRegs) { lds_read_row<kS>(sl, si); sp = sl; }
+          else sp = si;
+        }
+        (void)sl; (void)sp;
 #if (TOA_ROW_ABL & 1)   // ablation: no functor — the item's first scalars stand in for the row
         (void)xp;
 #pragma unroll
@@ -507,12 +505,20 @@ struct RowModel {
 #else
         if constexpr (kItemCost) {
           T ci = T(0);
-          if constexpr (WANT_H) F::template eval_item<true>(xp, d, p, ci, rv, Jv);
-          else F::template eval_item<false>(xp, d, p, ci, rv, static_cast<T(*)[kN]>(nullptr));
+          if constexpr (kS > 0) {
+            if constexpr (WANT_H) F::template eval_item<true>(xp, d, p, sp, ci, rv, Jv);
+            else F::template eval_item<false>(xp, d, p, sp, ci, rv, static_cast<T(*)[kN]>(nullptr));
+          } else {
+            if constexpr (WANT_H) F::template eval_item<true>(xp, d, p, ci, rv, Jv);
+            else F::template eval_item<false>(xp, d, p, ci, rv, static_cast<T(*)[kN]>(nullptr));
+          }
           csum += ci;
         } else if constexpr (kTableBytes > 0) {
           if constexpr (WANT_H) F::template eval_manual_tab<true>(xp, reinterpret_cast<const typename F::TabJet*>(stg + kGeom.table_off), d, p, rv, Jv);
           else F::template eval_manual_tab<false>(xp, nullptr, d, p, rv, static_cast<T(*)[kN]>(nullptr));
+        } else if constexpr (kS > 0) {
+          if constexpr (WANT_H) F::template eval_manual<true>(xp, d, p, sp, rv, Jv);
+          else F::template eval_manual<false>(xp, d, p, sp, rv, static_cast<T(*)[kN]>(nullptr));
         } else {
           if constexpr (WANT_H) F::template eval_manual<true>(xp, d, p, rv, Jv);
           else F::template eval_manual<false>(xp, d, p, rv, static_cast<T(*)[kN]>(nullptr));

@@ -584,6 +584,28 @@ int toa_model_compile(toa_handle h, int dtype, int num_params, int residuals_per
  * toa_jit_lbfgs_run, a loss on the handle, the *_prior, *_bounds and *_ragged entries, toa_jit_lm_run_split, toa_jit_lm_begin / step /
  * stop, toa_jit_eval.  toa_jit_spec is unchanged and no symbol is added: TOA_ABI_VERSION stays 7. */
 #define TOA_JIT_COST_GGN 5
+/* Multi-output second-order scalar cost — c_i = phi(u_i(x)) with a VECTOR inner function of K = residuals_per_item outputs, 1 <= K <= 8:
+ * multinomial / softmax regression (K logits), a Gaussian likelihood with mean and log-variance predictors, any multi-output GLM — run
+ * by LM / GN on the matrix-core Gram of the row models (ggn_multi_cost.hpp).  The body sees x[j], h[k], p[k] (and
+ * s[k] with a shared item table) on plain T.  It assigns `c`, the item's cost term, and inside `if (want_grad) { ... }`: gs[k] = dc/du_k
+ * for k < K; Hs[k][l] for l <= k, the LOWER triangle of the K x K curvature d2phi/du2 (the upper one is never read); J[k][a] = du_k/dx_a
+ * for EVERY k < K, a < n — assigned, not added.  The item contributes g += sum_k gs_k J_k and H += J^T Hs J through an unpivoted
+ * L D L^T of Hs whose pivots are clamped from below at wmin = 2^-60 (fp32) / 2^-200 (fp64) — the rule stands in ggn_multi_cost.hpp —,
+ * so H stays positive semi-definite: a Gauss-Newton door, NOT one for indefinite curvature.  g is sum_k gs_k J_k whatever was
+ * clamped.  With K = 1 this is TOA_JIT_COST_GGN operation for operation.  A singular parametrisation (all K logits of a softmax) is
+ * legal but ill-conditioned: use a reference class (K - 1 free logits).  Loops over k, l, a need COMPILE-TIME bounds; the lane holds J
+ * as K n scalars, so wide K x wide n spills (toa_jit_model_stats: scratch_bytes).
+ * The problem's cost is sum_i c_i as ONE residual, inlier ratio 1.  A Gaussian prior beside it (the *_prior entries) is the ridge
+ * term: cost += (1/2) |W (x - mu)|^2, g += W^T r, H += W^T W; nres stays 1.  A non-finite c, gs, Hs or J ends the problem with
+ * TOA_STOP_NAN_OR_INF.  Euclidean parameters, diff = TOA_DIFF_DEFAULT, large_n = 0, 1 <= num_params <= 63, fp32 and fp64; a shared
+ * item table (shared_scalars > 0) is taken.
+ * Served: toa_jit_lm_run, toa_jit_lm_run_prior, toa_jit_lm_run_shared (solver_type 0 and 1, a handle without a loss; never the automatic
+ * row-split), toa_jit_accumulate, toa_jit_accumulate_prior, toa_jit_accumulate_shared (g, cost, nres = 1 and, where H_dev is not NULL,
+ * the full symmetric [P][n][n] sum), toa_jit_model_stats, toa_jit_model_stats_prior, toa_jit_check_gradient (g only; not with a
+ * table).  Refused with TOA_E_UNSUPPORTED: solver_type 2 and 3 / toa_jit_gd_run / toa_jit_lbfgs_run, a loss on the handle, bounds,
+ * the *_ragged entries, toa_jit_lm_run_split, toa_jit_lm_begin / step / stop, toa_jit_eval.  toa_jit_spec is unchanged and no symbol is
+ * added: TOA_ABI_VERSION stays 7. */
+#define TOA_JIT_COST_GGN_MULTI 6
 /* Numerical differentiation (the reference's diff/num_diff.h: NumEval, EstimateNumJac, CreateNumDiffFunc1 / 2 with
  * Method::{kForward, kCentral, kFastCentral}): spec.diff != 0 differentiates a TOA_JIT_RESIDUAL or TOA_JIT_COST body by finite
  * differences with step spec.diff_h instead of Jets, so the body is only ever instantiated on plain T (S = T) and need not be

@@ -366,7 +366,7 @@ class RaggedJitModel;
 // What a body's text is (JitResidual's `kind`): the library's TOA_JIT_* by name
 enum JitKind {
   kJitResidual = TOA_JIT_RESIDUAL, kJitAccumulate = TOA_JIT_ACCUMULATE, kJitCost = TOA_JIT_COST, kJitCostGrad = TOA_JIT_COST_GRAD,
-  kJitCostHess = TOA_JIT_COST_HESS, kJitCostGgn = TOA_JIT_COST_GGN
+  kJitCostHess = TOA_JIT_COST_HESS, kJitCostGgn = TOA_JIT_COST_GGN, kJitCostGgnMulti = TOA_JIT_COST_GGN_MULTI
 };
 namespace detail {
 // What a second-order scalar cost (TOA_JIT_COST_HESS) does not take, in one sentence each
@@ -378,6 +378,11 @@ inline void refuse_cost_hess(const char* what) {
 inline void refuse_cost_ggn(const char* what) {
   throw std::invalid_argument(std::string("tinyopt_amd: a rank-one second-order scalar cost (TOA_JIT_COST_GGN) runs in the uniform one-launch form through "
                                           "Optimize (LM / GN), Accumulate and diff::CheckGradient only: ") + what);
+}
+// What a multi-output second-order scalar cost (TOA_JIT_COST_GGN_MULTI) does not take, in one sentence each
+inline void refuse_cost_ggn_multi(const char* what) {
+  throw std::invalid_argument(std::string("tinyopt_amd: a multi-output second-order scalar cost (TOA_JIT_COST_GGN_MULTI) runs in the uniform one-launch form "
+                                          "through Optimize (LM / GN), Accumulate and diff::CheckGradient only, with with_prior and a shared table: ") + what);
 }
 // What a model with a shared item table (JitResidual's shared_scalars > 0) does not take, in one sentence each
 inline void refuse_shared(const char* what) {
@@ -414,6 +419,13 @@ class JitResidual {
   //   one cost term per item, 1 <= n <= 63 in float and double; loops over a need compile-time bounds (stats().scratch_bytes shows a spill).
   //   GradientDescent, LBFGS, with_loss, with_prior, with_bounds, bind_ragged, host controls, the stepping Optimizer and diff::Eval /
   //   CalculateJac are refused (std::invalid_argument).
+  // kind = TOA_JIT_COST_GGN_MULTI (kJitCostGgnMulti): c_i = phi(u_i(x)) with a VECTOR inner function of K = residuals_per_item
+  //   outputs, 1 <= K <= 8 (softmax regression, mean + log-variance likelihoods) — the body assigns `c` and, inside `if (want_grad)`, gs[k] = dc/du_k,
+  //   Hs[k][l] for l <= k (the lower triangle of the K x K curvature) and J[k][a] = du_k/dx_a for every k < K, a < n; the item adds
+  //   g += sum_k gs_k J_k and H += J^T Hs J through a per-item L D L^T with pivots clamped at wmin: positive semi-definite; K = 1 is kJitCostGgn.
+  //   1 <= n <= 63; what kJitCostGgn takes, and with_prior (the ridge term: cost += 1/2 |W (x - mu)|^2, still one residual) and bind_shared;
+  //   GradientDescent, LBFGS, with_loss, with_bounds, bind_ragged, host controls, the stepping Optimizer and diff::Eval / CalculateJac are
+  //   refused (std::invalid_argument).
   // large_n = true: the model is compiled for the launch-per-phase pipeline of the wide problems instead of a wavefront per problem —
   //   n up to 1024 (float) / 512 (double), item_scalars up to 2048; TOA_JIT_RESIDUAL / TOA_JIT_ACCUMULATE, Euclidean, TOA_DIFF_DEFAULT.
   //   Optimize (LM / GN), Accumulate and diff::Eval / CalculateJac take it; with_loss, with_prior, with_bounds, bind_ragged, splits, the stepping
@@ -469,6 +481,7 @@ class JitResidual {
   RaggedJitModel<Scalar> bind_ragged(const std::vector<int64_t>& counts, const Scalar* data, const Scalar* header = nullptr) const {
     if (kind_ == TOA_JIT_COST_HESS) detail::refuse_cost_hess("no ragged batches (bind_ragged)");
     if (kind_ == TOA_JIT_COST_GGN) detail::refuse_cost_ggn("no ragged batches (bind_ragged)");
+    if (kind_ == TOA_JIT_COST_GGN_MULTI) detail::refuse_cost_ggn_multi("no ragged batches (bind_ragged)");
     if (kS_ > 0) detail::refuse_shared("no ragged batches (bind_ragged)");
     return RaggedJitModel<Scalar>(*this, counts, data, header);
   }
@@ -571,6 +584,7 @@ class BoundsTag {
       throw std::invalid_argument("tinyopt_amd::with_bounds: a model compiled with large_n takes no box bounds");
     if (res.kind() == TOA_JIT_COST_HESS) detail::refuse_cost_hess("no box bounds (with_bounds): they project the Gauss-Newton system of a residual model");
     if (res.kind() == TOA_JIT_COST_GGN) detail::refuse_cost_ggn("no box bounds (with_bounds)");
+    if (res.kind() == TOA_JIT_COST_GGN_MULTI) detail::refuse_cost_ggn_multi("no box bounds (with_bounds)");
     if (res.kind() == TOA_JIT_COST || res.kind() == TOA_JIT_COST_GRAD)
       throw std::invalid_argument("tinyopt_amd::with_bounds: a scalar cost model has no Gauss-Newton system to project");
     if (res.manifold() != TOA_MANIFOLD_EUCLID)
@@ -801,6 +815,12 @@ BatchOutput Optimize(std::vector<Scalar>& x, const Cost& cost, const Options& op
       if (lbfgs) detail::refuse_cost_ggn("no L-BFGS: run the same cost as kJitCostGrad");
       if (cost.loss_kind != TOA_LOSS_L2) detail::refuse_cost_ggn("no M-estimator (with_loss): a scalar cost has no residuals to robustify");
       if (options.has_host_controls()) detail::refuse_cost_ggn("no stepping form, so no host controls (stop callbacks, max_duration_ms, the log line)");
+    }
+    if (cost.kind() == TOA_JIT_COST_GGN_MULTI) {
+      if (gd) detail::refuse_cost_ggn_multi("no GradientDescent: run the same cost as kJitCostGrad");
+      if (lbfgs) detail::refuse_cost_ggn_multi("no L-BFGS: run the same cost as kJitCostGrad");
+      if (cost.loss_kind != TOA_LOSS_L2) detail::refuse_cost_ggn_multi("no M-estimator (with_loss): a scalar cost has no residuals to robustify");
+      if (options.has_host_controls()) detail::refuse_cost_ggn_multi("no stepping form, so no host controls (stop callbacks, max_duration_ms, the log line)");
     }
   }
   if (detail::has_bounds(cost)) {

@@ -311,6 +311,8 @@ class _LossMixin(_Model):
             _refuse_cost_hess("no M-estimator (with_loss): a scalar cost has no residuals to robustify")
         if loss not in (None, "l2") and _is_cost_ggn(self):
             _refuse_cost_ggn("no M-estimator (with_loss): a scalar cost has no residuals to robustify")
+        if loss not in (None, "l2") and _is_cost_ggn_multi(self):
+            _refuse_cost_ggn_multi("no M-estimator (with_loss): a scalar cost has no residuals to robustify")
         m = copy.copy(self)          # shares the device data
         m.loss, m.th = (loss if loss not in (None, "l2") else None), float(th)
         return m
@@ -427,6 +429,8 @@ class _BoundsMixin(_Model):
             _refuse_cost_hess("no box bounds (with_bounds): they project the Gauss-Newton system of a residual model")
         if _is_cost_ggn(self):
             _refuse_cost_ggn("no box bounds (with_bounds)")
+        if _is_cost_ggn_multi(self):
+            _refuse_cost_ggn_multi("no box bounds (with_bounds)")
         if res.kind in JitResidual.COST_KINDS:
             _refuse_bounds('a scalar cost model (kind="cost" / "cost_grad", GradientDescent) has no Gauss-Newton system to project')
         if res.manifold != "euclid":
@@ -524,6 +528,15 @@ def _is_cost_ggn(cost) -> bool:
     return cost.route == "jit" and getattr(cost.res, "kind", None) == "cost_ggn"
 
 
+def _refuse_cost_ggn_multi(what: str):
+    raise ValueError(f'a multi-output second-order scalar cost (kind="cost_ggn_multi") runs in the uniform one-launch form through Optimize '
+                     f"(LM / GN), accumulate and CheckGradient only, with with_prior and a shared table: {what}")
+
+
+def _is_cost_ggn_multi(cost) -> bool:
+    return cost.route == "jit" and getattr(cost.res, "kind", None) == "cost_ggn_multi"
+
+
 def _refuse_shared(what: str):
     raise ValueError(f"a model with a shared item table (shared_scalars > 0) runs in the uniform one-launch form through Optimize (LM / GN) and "
                      f"accumulate only: {what}")
@@ -588,6 +601,11 @@ _REFUSALS = {
     ("cost_ggn", "lbfgs"): 'no L-BFGS: run the same cost as kind="cost_grad"',
     ("cost_ggn", "splits"): _NO_SPLITS, ("cost_ggn", "host"): _NO_HOST, ("cost_ggn", "Optimizer"): _NO_STEPPING,
     **{("cost_ggn", what): f"no {what} (it has no residual rows: accumulate returns its value, its gradient and its Hessian)" for what in ("Eval", "CalculateJac")},
+    # a multi-output second-order scalar cost (kind="cost_ggn_multi"): LM / GN in the uniform one-launch form, with its prior and a table
+    ("cost_ggn_multi", "gd"): _NO_GD + ': run the same cost as kind="cost_grad"',
+    ("cost_ggn_multi", "lbfgs"): 'no L-BFGS: run the same cost as kind="cost_grad"',
+    ("cost_ggn_multi", "splits"): _NO_SPLITS, ("cost_ggn_multi", "host"): _NO_HOST, ("cost_ggn_multi", "Optimizer"): _NO_STEPPING,
+    **{("cost_ggn_multi", what): f"no {what} (it has no residual rows: accumulate returns its value, its gradient and its Hessian)" for what in ("Eval", "CalculateJac")},
     # a model with a shared item table (shared_scalars > 0): LM / GN and accumulate in the uniform one-launch form
     ("shared", "splits"): _NO_SPLITS, ("shared", "host"): _NO_HOST, ("shared", "gd"): _NO_GD, ("shared", "lbfgs"): "no L-BFGS",
     ("shared", "Optimizer"): _NO_STEPPING,
@@ -596,9 +614,10 @@ _REFUSALS = {
     **{("shared", what): f"no {what} (its kernels read replicated items: bind the table copied into every problem's items)" for what in ("Eval", "CalculateJac")},
 }
 _REFUSE_AS = {"ragged": _refuse_ragged, "bounds": _refuse_bounds, "prior": _refuse_prior, "large_n": _refuse_large_n, "cost_hess": _refuse_cost_hess,
-              "cost_ggn": _refuse_cost_ggn, "shared": _refuse_shared}
+              "cost_ggn": _refuse_cost_ggn, "cost_ggn_multi": _refuse_cost_ggn_multi, "shared": _refuse_shared}
 _OPTIMIZE_REFUSES = (("shared", "lbfgs"), ("shared", "gd"), ("shared", "splits"), ("shared", "host"),
                      ("cost_ggn", "lbfgs"), ("cost_ggn", "gd"), ("cost_ggn", "splits"), ("cost_ggn", "host"),
+                     ("cost_ggn_multi", "lbfgs"), ("cost_ggn_multi", "gd"), ("cost_ggn_multi", "splits"), ("cost_ggn_multi", "host"),
                      ("cost_hess", "lbfgs"), ("bounds", "lbfgs"), ("prior", "lbfgs"), ("large_n", "lbfgs"), ("not_cost", "lbfgs"),
                      ("lbfgs_cost", "host"), ("lbfgs_cost", "splits"), ("lbfgs_cost", "grad_clipping"), ("lbfgs_cost", "lbfgs.history"),
                      ("lbfgs_cost", "lbfgs.c1"), ("lbfgs_cost", "lbfgs.shrink"),
@@ -607,9 +626,9 @@ _OPTIMIZE_REFUSES = (("shared", "lbfgs"), ("shared", "gd"), ("shared", "splits")
                      ("bounds", "splits"), ("bounds", "host"), ("bounds", "gd"), ("prior", "splits"), ("prior", "host"), ("prior", "gd"),
                      ("large_n", "splits"), ("large_n", "host"), ("large_n", "gd"), ("large_n", "capture"), ("numeric", "host"), ("numeric", "splits"),
                      ("gd_cost", "host"), ("gd_cost", "splits"), ("stepping", "out with host controls"))
-_OPTIMIZER_REFUSES = tuple((who, "Optimizer") for who in ("shared", "lbfgs", "cost_hess", "cost_ggn", "ragged", "bounds", "prior", "numeric", "large_n"))
+_OPTIMIZER_REFUSES = tuple((who, "Optimizer") for who in ("shared", "lbfgs", "cost_hess", "cost_ggn", "cost_ggn_multi", "ragged", "bounds", "prior", "numeric", "large_n"))
 _CHECK_GRADIENT_REFUSES = tuple((who, "CheckGradient") for who in ("shared", "bounds", "prior", "ragged", "large_n"))
-_ROWS_REFUSES = {what: (("shared", what), ("cost_hess", what), ("cost_ggn", what), ("bounds", what), ("prior", what)) for what in ("Eval", "CalculateJac")}
+_ROWS_REFUSES = {what: (("shared", what), ("cost_hess", what), ("cost_ggn", what), ("cost_ggn_multi", what), ("bounds", what), ("prior", what)) for what in ("Eval", "CalculateJac")}
 
 
 def _who(cost, gd: bool = False, lbfgs: bool = False) -> set:
@@ -634,6 +653,8 @@ def _who(cost, gd: bool = False, lbfgs: bool = False) -> set:
         who.add("cost_hess")
     if _is_cost_ggn(cost):
         who.add("cost_ggn")
+    if _is_cost_ggn_multi(cost):
+        who.add("cost_ggn_multi")
     if cost.route != "ba_lists":   # (it honours max_duration_ms itself; every other family goes to the stepping form for host controls)
         who.add("stepping")
     return who
@@ -928,6 +949,31 @@ class JitResidual:
             if (want_grad) { gs = -y * (T(1) - s); hs = s * (T(1) - s); for (int a = 0; a < 50; ++a) J[a] = p[a]; }''',
             n=50, item_scalars=51, kind="cost_ggn", dtype=torch.float32)
 
+    Multi-output second-order scalar costs (DESIGN section 22) — ``kind="cost_ggn_multi"``: a cost ``c_i = phi(u_i(x))`` with a VECTOR
+    inner function of ``K = residuals_per_item`` outputs, 1 <= K <= 8: multinomial / softmax regression, a Gaussian likelihood with
+    mean and log-variance predictors, any multi-output GLM.  The body assigns ``c`` and, inside ``if (want_grad) { ... }``,
+    ``gs[k]`` = dc/du_k, ``Hs[k][l]`` for l <= k (the LOWER triangle of the K x K curvature; the upper one is never read) and
+    ``J[k][a]`` = du_k/dx_a for every k < K, a < n (assigned, not added).  The item contributes ``g += sum_k gs_k J_k`` and
+    ``H += J^T Hs J`` through an unpivoted L D L^T of ``Hs`` per item whose pivots are clamped from below at wmin (2^-60 / 2^-200), so H
+    stays positive semi-definite — a Gauss-Newton door, not one for indefinite curvature; K = 1 is ``cost_ggn`` bit for bit.  A
+    singular parametrisation (all K logits of a softmax) is legal but ill-conditioned: use a reference class (K - 1 free logits).
+    The lane holds ``J`` as K n scalars: wide K x wide n spills (``stats()["scratch_bytes"]``).  Everything ``cost_ggn`` takes, and
+    ``with_prior(mu, W)`` — the ridge term: cost += 1/2 |W (x - mu)|^2, g += W^T r, H += W^T W, still ONE residual — and
+    ``shared_scalars``; ``with_loss``, ``with_bounds``, ``bind_ragged`` and the rest are refused with a sentence.  Three-class softmax
+    regression with a reference class, d = 25 features (n = 50; an item = 25 features + the class 0, 1 or 2)::
+
+        softmax = ta.JitResidual('''
+            T u0 = 0, u1 = 0; for (int j = 0; j < 25; ++j) { u0 += p[j] * x[j]; u1 += p[j] * x[25 + j]; }
+            const T mx = fmax(T(0), fmax(u0, u1)), e0 = exp(u0 - mx), e1 = exp(u1 - mx), er = exp(-mx), z = e0 + e1 + er;
+            const T q0 = e0 / z, q1 = e1 / z, y = p[25];
+            c = log(z) + mx - (y == T(0) ? u0 : y == T(1) ? u1 : T(0));
+            if (want_grad) {
+              gs[0] = q0 - (y == T(0) ? T(1) : T(0)); gs[1] = q1 - (y == T(1) ? T(1) : T(0));
+              Hs[0][0] = q0 * (T(1) - q0); Hs[1][0] = -q0 * q1; Hs[1][1] = q1 * (T(1) - q1);
+              for (int a = 0; a < 25; ++a) { J[0][a] = p[a]; J[0][25 + a] = T(0); J[1][a] = T(0); J[1][25 + a] = p[a]; }
+            }''', n=50, item_scalars=26, residuals_per_item=2, kind="cost_ggn_multi", dtype=torch.float32)
+        out = ta.Optimize(w, softmax.bind(samples).with_prior(mu, lam), ta.Options())   # lam [P, 50]: sqrt of the ridge weights
+
     Numerical differentiation (the reference's diff/num_diff.h: ``NumEval`` / ``CreateNumDiffFunc1/2``) — ``diff="forward"``,
     ``"central"`` or ``"fast_central"`` with step ``diff_h`` (0 = FloatEpsilon: 1e-4 in float32, 1e-7 in float64) differentiates a
     ``kind="residual"`` or ``kind="cost"`` body by finite differences instead of Jets: the body is only ever instantiated on the
@@ -963,10 +1009,11 @@ class JitResidual:
     solve.  Without ``large_n`` a model of 64 parameters is refused as before.  ``stats()`` then describes the rows kernel."""
 
     MANIFOLDS = {"euclid": 0, "se3": 1, "user": 2}
-    KINDS = {"residual": 0, "accumulate": 1, "cost": 2, "cost_grad": 3, "cost_hess": 4, "cost_ggn": 5}
+    KINDS = {"residual": 0, "accumulate": 1, "cost": 2, "cost_grad": 3, "cost_hess": 4, "cost_ggn": 5, "cost_ggn_multi": 6}
     COST_KINDS = ("cost", "cost_grad")   # the first-order kinds (GradientDescent); "cost_hess" runs under LM / GN
     COST_HESS_MAX_N = 12
     COST_GGN_MAX_N = 63
+    COST_GGN_MULTI_MAX_K = 8
     DIFFS = {"ad": 0, "forward": 1, "central": 2, "fast_central": 3}
 
     def __init__(self, body: str, n: int, item_scalars: int, residuals_per_item: int = 1, header_scalars: int = 0,
@@ -1020,6 +1067,18 @@ class JitResidual:
                 _refuse_cost_ggn(f"an item has one cost term: residuals_per_item = 1, not {self.kR}")
             if not 1 <= self.n <= self.COST_GGN_MAX_N:
                 _refuse_cost_ggn(f"1 <= n <= {self.COST_GGN_MAX_N} in float32 and float64 (one wavefront per problem), not n = {self.n}")
+        if kind == "cost_ggn_multi":   # (the library refuses the same, toa_model_compile_ex: here before anything is compiled)
+            if manifold != "euclid":
+                _refuse_cost_ggn_multi(f"Euclidean parameters only, not manifold={manifold!r}")
+            if diff != "ad":
+                _refuse_cost_ggn_multi(f'the body brings its own derivatives, nothing is differentiated: diff="ad" only, not diff={diff!r}')
+            if self.large_n:
+                _refuse_cost_ggn_multi("no large_n (the launch-per-phase pipeline is for residual models)")
+            if not 1 <= self.n <= self.COST_GGN_MAX_N:
+                _refuse_cost_ggn_multi(f"1 <= n <= {self.COST_GGN_MAX_N} in float32 and float64 (one wavefront per problem), not n = {self.n}")
+            if not 1 <= self.kR <= self.COST_GGN_MULTI_MAX_K:
+                _refuse_cost_ggn_multi(f"residuals_per_item is K, the outputs per item: 1 <= K <= {self.COST_GGN_MULTI_MAX_K} (an item is K rows of the "
+                                       f"Gram), not {self.kR}")
         if self.large_n:   # (the library refuses the same, toa_model_compile_ex: here before anything is compiled)
             if kind in self.COST_KINDS:
                 _refuse_large_n('no scalar costs (kind="cost" / "cost_grad") and no GradientDescent')
@@ -1098,6 +1157,8 @@ class JitResidual:
             _refuse_cost_hess("no ragged batches (bind_ragged)")
         if self.kind == "cost_ggn":
             _refuse_cost_ggn("no ragged batches (bind_ragged)")
+        if self.kind == "cost_ggn_multi":
+            _refuse_cost_ggn_multi("no ragged batches (bind_ragged)")
         if getattr(self, "kS", 0):
             _refuse_shared("no ragged batches (bind_ragged)")
         return RaggedJitModel(self, data, counts, offsets, header)
@@ -1840,7 +1901,7 @@ def CheckGradient(model: "JitModel", x: torch.Tensor, eps: Optional[float] = Non
                                          JitResidual.DIFFS[method], int(bool(check_H)), dist.data_ptr(), ok.data_ptr()))
     if eps is None:
         e = 1e-2 if x.dtype == torch.float32 else 1e-5
-    if check_H and (_is_cost_hess(model) or _is_cost_ggn(model)):
+    if check_H and (_is_cost_hess(model) or _is_cost_ggn(model) or _is_cost_ggn_multi(model)):
         # The body's H against central differences of the body's OWN gradient with the checker's step eps / 10 (gradient_check.h:96,201):
         # 2 n Accumulate calls on shifted copies of x, no device code of its own.  Column a of the numeric H is (g(x + h e_a) - g(x - h e_a)) / (2 h).
         n, step = model.n, e / 10.0

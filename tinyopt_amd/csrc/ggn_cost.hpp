@@ -77,11 +77,11 @@ struct GgnRowFunctor {
   }
 };
 
-// The Accumulate seam (toa_jit_accumulate on a TOA_JIT_COST_GGN model): accumulate_kernel's arguments and its loop, with H_ optional —
+// The Accumulate seam (toa_jit_accumulate on a TOA_JIT_COST_GGN / TOA_JIT_COST_GGN_MULTI model): accumulate_kernel's arguments and its loop, with H_ optional —
 // g [P][n], the full symmetric H [P][n][n] when H_ is not null, cost [P] = sum_i c_i, nres [P] = 1.
 template <typename Model>
 __global__ void __launch_bounds__(256) ggn_accumulate_kernel(const void* data_, const void* x_, long long P, int n, int m, int want_grad, void* g_,
-                                                             void* H_, double* cost, int* nres, int lds_per_wave, int, double TOA_SHARED_KARG) {
+                                                             void* H_, double* cost, int* nres, int lds_per_wave, int, double TOA_PRIOR_KARG TOA_SHARED_KARG) {
   using T = typename Model::Scalar;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -92,6 +92,9 @@ __global__ void __launch_bounds__(256) ggn_accumulate_kernel(const void* data_, 
   model.set_shared(shr);
 #endif
   WaveLds<T> L = WaveLds<T>::carve(model_bind_stage(model, smem + size_t(wave) * lds_per_wave, n), n);
+#ifdef TOA_PRIOR
+  model.set_prior(pri, L.M, L.LD);   // (TOA_JIT_COST_GGN_MULTI only: ggn_multi_cost.hpp; PriorModel's item-cost branch, prior.hpp)
+#endif
   for (long long p = (long long)blockIdx.x * 4 + wave; p < P; p += (long long)gridDim.x * 4) {
     wave_sync();
     L.xs[lane] = lane < n ? X[size_t(p) * n + lane] : T(0);

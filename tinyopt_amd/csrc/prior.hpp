@@ -38,6 +38,12 @@ struct PriorArgs {
 // whatever wave runs the problem), and the sums over the k rows run in row order in every lane.  n is the model's compile-time kN,
 // k a kernel argument: no register array is indexed by a run-time value.  The model's memo keeps the items' Gram only; the prior
 // is recomputed at the restored x.
+// a base that sums its items' own cost terms (RowModel over an item-cost functor: ggn_multi_cost.hpp)
+template <typename M, typename = void>
+struct ModelItemCost { static constexpr bool value = false; };
+template <typename M>
+struct ModelItemCost<M, std::enable_if_t<M::kItemCost>> { static constexpr bool value = true; };
+
 template <typename Base>
 struct PriorModel : Base {
   using T = typename Base::Scalar;
@@ -91,9 +97,15 @@ struct PriorModel : Base {
     if constexpr (WANT_GRAD) {
       if (in) { L.g[lane] = L.g[lane] + gp; L.hd[lane] = L.hd[lane] + hp; }
     }
-    cost = cost + cp;
-    nres += k;
-    if (Base::ninl >= 0) Base::ninl += k;   // (-1: no loss, every residual an inlier)
+    if constexpr (ModelItemCost<Base>::value) {
+      // a scalar cost: the prior is the ridge term (1/2) |W (x - mu)|^2 (the halving is exact), so that g += W^T r stays the gradient
+      // of the reported cost and H += W^T W its Hessian; the cost stays ONE residual, the inlier count is left alone
+      cost = cost + T(0.5) * cp;
+    } else {
+      cost = cost + cp;
+      nres += k;
+      if (Base::ninl >= 0) Base::ninl += k;   // (-1: no loss, every residual an inlier)
+    }
     wave_sync();
   }
   __device__ __forceinline__ void accumulate(WaveLds<T>& L, int n, int lane, T& cost, int& nres) {

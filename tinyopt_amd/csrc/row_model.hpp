@@ -188,7 +188,7 @@ template <typename F, typename = void>
 struct FunctorTable { static constexpr int bytes = 0; };
 template <typename F>
 struct FunctorTable<F, std::enable_if_t<F::kTable>> { static constexpr int bytes = F::kTableBytes; };
-// Extension point (ggn_cost.hpp): a functor with kItemCost supplies every item's COST TERM itself, beside its row —
+// Extension point (ggn_cost.hpp, ggn_multi_cost.hpp; DESIGN sections 20, 22): a functor with kItemCost supplies every item's COST TERM itself, beside its kR rows —
 //   template <bool want_grad> eval_item(x, h, p, T& c, T* r, T (*J)[kN])
 // The pass then sums c per lane and returns the wave's sum on both passes: the problem's cost is that sum as ONE residual, the
 // Gram's (r, r) entry and the rows' squared norms are not read, and the model keeps no memo (its cost is no Gram entry).  No
@@ -211,7 +211,7 @@ struct RowModel {
   static_assert(kXdim <= 64, "stored scalars of x: one per lane");
   static constexpr int kTableBytes = FunctorTable<F>::bytes;
   static constexpr bool kItemCost = FunctorItemCost<F>::value;
-  static_assert(!kItemCost || (!ROBUST && MANIFOLD == 0 && kTableBytes == 0 && F::kR == 1), "an item-cost functor: plain Euclidean rows, one per item");
+  static_assert(!kItemCost || (!ROBUST && MANIFOLD == 0 && kTableBytes == 0), "an item-cost functor: plain Euclidean rows");
   static constexpr int kN = F::kN, kR = F::kR, kD = F::kD;
   static constexpr int kNmax = THIN > 0 ? 16 * NBM + THIN - 1 : 16 * NBM - 1;
   static constexpr int kNpad = (kNmax + 7) & ~7;
